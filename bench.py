@@ -14,11 +14,20 @@ already resident in HBM.  Algorithmic bytes per step = P * (K+1) * L * 8
 sharded 16 per GPU (`-pa` segments mapped to devices), no data-path
 collective -> weak scaling; value = all ranks' bytes / max-over-ranks time.
 
-Extra JSON objects: `roofline` (dominant kernel, HIP-event time on the
-handle's stream vs 8 TB/s HBM peak; traffic from the committed rocprofv3 PMC
-pass when one matches this workload) and `cpu_baseline` (the reference's
-single-thread Updater decode+fold loop restated in C, oracle/, timed on this
-host on a bounded sample; rank 0, N=1 only).
+A plain run does only what the headline needs: set up, warm up, time the
+steps, write the outputs (--dump-outputs DIR: what the last timed step left,
+as .npy) and print the line.  Its `roofline` object is the timed launches'
+own HIP-event span on the handle's stream vs 8 TB/s HBM peak (traffic from the
+committed rocprofv3 PMC pass when one matches this workload); it costs no run
+of its own.
+
+--full adds everything else, after the headline and never in its value: the
+oracle check of every timed partition (`verified`), the rest of the round,
+the publish / per-arrival / host-inclusive / Middleware / JNI legs, the other
+configs and `cpu_baseline` (the reference's single-thread Updater decode+fold
+loop restated in C, oracle/, timed on this host on a bounded sample; rank 0,
+N=1 only), and at N > 1 the cross-GPU legs.  The --no-* options trim a --full
+run.
 """
 from __future__ import annotations
 
@@ -120,6 +129,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else: the oracle check of the timed sums, the "
+                         "rest of the round, the side legs, the other configs, the CPU baseline and (N>1) the "
+                         "cross-GPU legs; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (each partition's sum, a fixed "
+                         "seeded sample of it when the whole exceeds the size cap) as DIR/<name>.npy, float64")
     ap.add_argument("--strong", action="store_true",
                     help="fixed total work: the config's partitions are split over the ranks "
                          "(default: weak scaling, the config per GPU)")
@@ -1757,8 +1773,44 @@ def plumbing_selftest(args) -> None:
     dist.destroy_process_group()
 
 
+DUMP_CAP_BYTES = 48 << 20     # all of a run's dumped arrays together stay under 64 MB
+DUMP_SEED = 0x1B15            # the sample's element choice: fixed, so two builds dump the same elements
+
+
+def dump_sample_index(P: int, L: int) -> np.ndarray | None:
+    """Which elements of every partition's sum --dump-outputs keeps: None for
+    all of them when P x L doubles fit DUMP_CAP_BYTES, else a sorted, seeded
+    choice (the same for every partition and every run of these shapes) that
+    always holds the first and the last element."""
+    per_part = DUMP_CAP_BYTES // 8 // P
+    if L <= per_part:
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = rng.choice(L - 2, size=per_part - 2, replace=False) + 1
+    return np.sort(np.concatenate(([0], idx, [L - 1]))).astype(np.int64)
+
+
+def dump_outputs(path: str, name: str, read_partition, P: int, L: int) -> dict:
+    """Write the last timed step's result -- partition q's sum of L doubles is
+    read_partition(q), as the caller of the timed call would read it -- to
+    path/name.npy: float64, shape (P, L), or (P, S) over dump_sample_index's
+    elements."""
+    idx = dump_sample_index(P, L)
+    out = np.empty((P, L if idx is None else idx.size), dtype=np.float64)
+    for q in range(P):
+        v = read_partition(q)
+        out[q] = v if idx is None else v[idx]
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / f"{name}.npy", out)
+    return {"file": f"{name}.npy", "shape": list(out.shape), "dtype": "float64",
+            "sampled": idx is not None, "sample_seed": None if idx is None else DUMP_SEED}
+
+
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
     launched = "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
         sys.exit(spawn_ranks(args.gpus))
@@ -1864,12 +1916,27 @@ def main():
     total_bytes = bytes_step * args.steps * world
     value = total_bytes / dt_max / 1e9
 
-    # every partition of the last timed launch against the oracle's checksum
-    # of its fixed-order sum; at N > 1 each rank checks its own block and rank
-    # 0 gathers the counts
+    # what the last timed launch left, before any later leg folds again: the
+    # sums as their caller reads them (AGG through ipls_agg_read, or the
+    # big-endian bytes the launch wrote, decoded)
+    dumped = None
+    if args.dump_outputs:
+        if args.be:
+            def read_sum(q):
+                o = (dsts[q] - int(out_arena.data_ptr())) // 8
+                return out_arena[o:o + L].cpu().numpy().view(">f8").astype(np.float64)
+        else:
+            def read_sum(q):
+                return agg.read(q)
+        dumped = dump_outputs(args.dump_outputs, "sums" if world == 1 else f"sums_rank{rank}", read_sum, P, L)
+        progress(f"outputs written to {args.dump_outputs}")
+
+    # --full: every partition of the last timed launch against the oracle's
+    # checksum of its fixed-order sum; at N > 1 each rank checks its own block
+    # and rank 0 gathers the counts
     verified = None
     ver_parts = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         from oracle import oracle as O   # checker only: the oracle's checksum of the fixed-order sum
         ok = 0
         for q in range(P):
@@ -1886,9 +1953,9 @@ def main():
         verified = good == total
         ver_parts = f"{good}/{total}"
 
-    # the rest of an aggregation round on the same handle (round_leg)
+    # --full: the rest of an aggregation round on the same handle (round_leg)
     round_info = None
-    if not args.be:
+    if args.full and not args.be:
         try:
             round_info = round_leg(ipls, torch, agg, rows, P, L, K, stream, kern_ms, build, args.config)
         except Exception as e:   # a side measurement never costs the headline line
@@ -1937,6 +2004,8 @@ def main():
         }
         if rccl is not None:
             out["rccl"] = rccl
+        if dumped is not None:
+            out["outputs"] = dumped
         if round_info:
             out["round"] = round_info
         def side(fn, *a, **kw):
@@ -1947,19 +2016,20 @@ def main():
                 return {"error": f"{type(e).__name__}: {e}"}
             finally:
                 progress(f"{fn.__name__} done")
-        if world == 1 and not args.be:
+        solo = args.full and world == 1    # the N=1 legs after the headline
+        if solo and not args.be:
             out["publish"] = side(publish_leg, ipls, torch, agg, stream, L, verify=not args.no_verify)
-        if world == 1 and not args.be and not args.no_per_arrival:
+        if solo and not args.be and not args.no_per_arrival:
             out["per_arrival"] = side(per_arrival_leg, ipls, torch, agg, rows, P, L, K, stream, not args.no_verify)
-        if world == 1 and not args.no_e2e:
+        if solo and not args.no_e2e:
             out["host_inclusive"] = side(host_inclusive, ipls, ipls.Aggregator, L, K, args.e2e_reps, local)
-        if world == 1 and not args.no_e2e and not args.no_middleware:
+        if solo and not args.no_e2e and not args.no_middleware:
             out["middleware_socket"] = side(middleware_socket_leg, ipls, torch, local, verify=not args.no_verify)
-        if world == 1 and not args.no_e2e:
+        if solo and not args.no_e2e:
             out["jni_heap"] = side(jni_heap_leg)
-        if world == 1 and not args.no_cpu_baseline:
+        if solo and not args.no_cpu_baseline:
             out["cpu_baseline"] = side(cpu_baseline, L, K, args.cpu_passes)
-        if world == 1 and not args.no_other_configs and args.config == "C" and not args.be:
+        if solo and not args.no_other_configs and args.config == "C" and not args.be:
             # the other single-GPU BASELINE configs, measured in the same run (never the value)
             del arena, rows
             torch.cuda.empty_cache()
@@ -1981,7 +2051,7 @@ def main():
         torch.cuda.empty_cache()
         out["be_schedule_ab"] = side(be_schedule_ab, ipls, torch, local, verify=not args.no_verify)
     dog = None
-    if world > 1 and not args.be and not (args.no_replica_leg and args.no_ulp_leg and args.no_strong_leg
+    if args.full and world > 1 and not args.be and not (args.no_replica_leg and args.no_ulp_leg and args.no_strong_leg
                                           and args.no_multi_leg
                                           and args.no_e2e):
         # the multi-rank side legs are extra measurements: a watchdog ends a

@@ -148,9 +148,13 @@ def test_full_size_checksum_spot(golden_meta):
 def test_ethmodel_fixture(ethmodel, golden_meta):
     assert ethmodel.shape == (443610,)
     assert np.isfinite(ethmodel).all()
-    ref = O.ethmodel_path()
-    if ref is not None:       # build container: fixture == the reference file's [D payload
-        assert_bits_equal(O.parse_ethmodel(ref.read_bytes()), ethmodel, "ETHModel")
+    # the reference file is its 136-byte stream header (ref_ethmodel_head.bin,
+    # which ends with the [D element count) followed by the doubles: parsed as
+    # that file, the stored bytes must give the fixture back
+    head = (GOLDEN / "ref_ethmodel_head.bin").read_bytes()
+    raw = gzip.decompress((GOLDEN / "ethmodel.f64be.gz").read_bytes())
+    assert struct.unpack(">i", head[-4:])[0] == ethmodel.size
+    assert_bits_equal(O.parse_ethmodel(head + raw), ethmodel, "ETHModel")
 
 
 def test_config_a_oracle(ethmodel, golden_meta):

@@ -33,17 +33,17 @@ for s in $STEPS; do
       ;;
     dsched)
       for i in 1 2 3; do
-        timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs \
+        timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs \
           --no-per-arrival --be-schedule-ab >> $O/be_schedule_ab.jsonl 2>> $O/be_schedule_ab.err || exit 22
       done
       ;;
     dpmc)
       cd /tmp
       timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $O/pmc_fetch_D -o run -- \
-        python3 $R/bench.py --config D --be --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
+        python3 $R/bench.py --full --config D --be --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
         --steps 3 --warmup 1 > $O/pmc_fetch_D.log 2>&1 || exit 23
       timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d $O/pmc_write_D -o run -- \
-        python3 $R/bench.py --config D --be --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
+        python3 $R/bench.py --full --config D --be --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
         --steps 3 --warmup 1 > $O/pmc_write_D.log 2>&1 || exit 24
       cd $R
       ;;
@@ -71,7 +71,7 @@ for s in $STEPS; do
     btrace)   # config B under rocprofv3 --kernel-trace --stats: the kernel's own duration
       cd /tmp
       timeout -k 10 200 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/trace_B -o run -- \
-        python3 $R/bench.py --config B --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival \
+        python3 $R/bench.py --full --config B --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival \
         > $O/bench_B_trace.json 2> $O/bench_B_trace.err || exit 36
       cd $R
       ;;
@@ -109,10 +109,10 @@ for s in $STEPS; do
     fpmc)     # config F (16 x 8M x 64, one GPU's slice) PMC passes
       cd /tmp
       timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $O/pmc_fetch_F -o run -- \
-        python3 $R/bench.py --config F --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
+        python3 $R/bench.py --full --config F --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
         --steps 3 --warmup 1 > $O/pmc_fetch_F.log 2>&1 || exit 47
       timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d $O/pmc_write_F -o run -- \
-        python3 $R/bench.py --config F --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
+        python3 $R/bench.py --full --config F --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
         --steps 3 --warmup 1 > $O/pmc_write_F.log 2>&1 || exit 48
       cd $R
       ;;
@@ -134,34 +134,34 @@ for s in $STEPS; do
     bpmc)
       cd /tmp
       timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $O/pmc_fetch_B -o run -- \
-        python3 $R/bench.py --config B --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
+        python3 $R/bench.py --full --config B --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
         --steps 20 --warmup 2 > $O/pmc_fetch_B.log 2>&1 || exit 26
       timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d $O/pmc_write_B -o run -- \
-        python3 $R/bench.py --config B --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
+        python3 $R/bench.py --full --config B --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival --no-verify \
         --steps 20 --warmup 2 > $O/pmc_write_B.log 2>&1 || exit 27
       cd $R
       ;;
     rehearsal)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs \
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-other-configs \
         --no-per-arrival --multi-rehearsal > $O/bench_multi_rehearsal.json 2> $O/bench_multi_rehearsal.err || exit 28
       ;;
     bench)
-      timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 29
+      timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 29
       ;;
     repeat)   # three default bench runs (no CPU baseline) on one box: the process-to-process spread
       for i in 1 2 3; do
-        timeout -k 10 400 python bench.py --no-cpu-baseline >> $O/bench_repeat.jsonl 2>> $O/bench_repeat.err || exit 50
+        timeout -k 10 400 python bench.py --full --no-cpu-baseline >> $O/bench_repeat.jsonl 2>> $O/bench_repeat.err || exit 50
       done
       ;;
     dprobe)   # config D in the default line vs the A/B leg, same process: with and without the other legs
-      timeout -k 10 400 python bench.py --no-cpu-baseline --no-e2e --no-per-arrival --be-schedule-ab \
+      timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-e2e --no-per-arrival --be-schedule-ab \
         >> $O/dprobe.jsonl 2>> $O/dprobe.err || exit 30
-      timeout -k 10 500 python bench.py --be-schedule-ab >> $O/dprobe.jsonl 2>> $O/dprobe.err || exit 31
+      timeout -k 10 500 python bench.py --full --be-schedule-ab >> $O/dprobe.jsonl 2>> $O/dprobe.err || exit 31
       ;;
     gloo)     # the N>1 bench legs over gloo with every rank on the one GPU (a code-path rehearsal)
       for n in 2 4; do
         timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-          --master-port $((29500 + n)) bench.py --gpus $n --dist-backend gloo --steps 20 --warmup 5 \
+          --master-port $((29500 + n)) bench.py --full --gpus $n --dist-backend gloo --steps 20 --warmup 5 \
           > $O/bench_gloo$n.json 2> $O/bench_gloo$n.err || exit 33
       done
       ;;
@@ -192,7 +192,7 @@ for s in $STEPS; do
       ;;
     gloo8)    # the N = 8 bench over gloo with every rank on GPU 0 (rehearsal of the 8-GPU code path and memory)
       timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-        --master-port 29508 bench.py --gpus 8 --dist-backend gloo --steps 10 --warmup 2 \
+        --master-port 29508 bench.py --full --gpus 8 --dist-backend gloo --steps 10 --warmup 2 \
         > $O/bench_gloo8.json 2> $O/bench_gloo8.err || exit 43
       ;;
     soak)     # random call sequences: 40 seeds at production bucket lengths, 400 short ones

@@ -10,7 +10,7 @@ R=$(pwd)
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-LEAN="--no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival"
+LEAN="--full --no-cpu-baseline --no-e2e --no-other-configs --no-per-arrival"
 cd /tmp
 if [ -z "$SKIP_TRACE" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/trace_C -o run -- \
