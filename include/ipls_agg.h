@@ -99,6 +99,16 @@ extern "C" {
 #define IPLS_HOST_TEXT    7  /* output only: host bytes of a base64url pubsub text
                                 (Marshall_Packet's String, MyIPFSClass.java:1016)           */
 #define IPLS_DEV_TEXT     8  /* output only: the same text in device memory                  */
+#define IPLS_HOST_DARR    9  /* host byte[] of a Java-serialised double[] (the single-partition
+                                hand-over file, MyIPFSClass.java:261-270); n = byte length  */
+#define IPLS_HOST_DLIST  10  /* host byte[] of a Java-serialised ArrayList<Double> (`<ID>Model`,
+                                `<ID>ETHModel`, IPLS.java:547-558, 2255-2273; read by
+                                DownloadParameters, MyIPFSClass.java:376-385); n = byte
+                                length; ipls_agg_load_model only                            */
+
+/* ---- ipls_agg_load_saved modes ---- */
+#define IPLS_SAVED_SET    0  /* target[p] = file[p]                                          */
+#define IPLS_SAVED_BLEND  1  /* target[p][i] = a*target[p][i] + b*file[p][i]  (Updater.java:65-69) */
 
 /* ---- fold start modes ---- */
 #define IPLS_START_ACCUM  0  /* fold into the target's current value (Updater arrival fold)     */
@@ -138,6 +148,11 @@ typedef struct ipls_agg_cfg {
  * waits for its callback) and may call into the same handle. */
 typedef int (*ipls_chunk_sink)(void *ctx, const double *values, int64_t offset, int64_t n);
 typedef int (*ipls_chunk_source)(void *ctx, void *dst, int64_t offset, int64_t n);
+/* The sink of ipls_agg_save_model_chunked: n bytes of the file at byte `offset`,
+ * valid during the call only.  Same rules as ipls_chunk_sink.  (The prototype
+ * spells the parameter IPLS_BYTE_SINK_FN *, the same type as ipls_byte_sink.) */
+typedef int IPLS_BYTE_SINK_FN(void *ctx, const uint8_t *bytes, int64_t offset, int64_t n);
+typedef IPLS_BYTE_SINK_FN *ipls_byte_sink;
 
 /* ABI version of the loaded library (IPLS_AGG_ABI_VERSION). */
 int ipls_agg_abi_version(void);
@@ -166,7 +181,10 @@ int ipls_agg_flat_size(const ipls_agg *h, int64_t *n);
 
 /* InitializeWeights(List<Double> Model), IPLS.java:1880-1901: Weights and
  * Weight_Address get the model values with count slot 0.0; AGG, REP = 0.
- * src: HOST_F64 / HOST_BE (read_file format, IPLS.java:2000-2008) / DEV_*. */
+ * src: HOST_F64 / HOST_BE (read_file format, IPLS.java:2000-2008) / DEV_* /
+ * HOST_DLIST (n = byte length: the ArrayList<Double> that DownloadParameters
+ * reads, IPLS.java:567; its element records are checked on the device before
+ * anything is written, IPLS_E_FORMAT leaves every accumulator as it was). */
 int ipls_agg_load_model(ipls_agg *h, const void *src, int64_t n, int src_kind);
 
 /* OrganizeGradients (IPLS.java:1018-1040) for partition p: dst gets
@@ -185,7 +203,8 @@ int ipls_agg_update_gradient(ipls_agg *h, const void *flat, int64_t n, int src_k
  * 74-137 AGG branches): target[p][i] = target[p][i] + g[i], i < L_p.
  * n = #doubles (F64/BE kinds) or frame byte length (FRAME kind; the frame's
  * n field must be >= L_p; PAIR kind: its double[] must be >= L_p).  Returns IPLS_E_RANGE when the bucket is shorter
- * than L_p.  Also Collect_Replicas (IPLS.java:1217-1241) with target REP. */
+ * than L_p.  Also Collect_Replicas (IPLS.java:1217-1241) with target REP.
+ * DARR kind (n = byte length): like PAIR, its double[] must be >= L_p. */
 int ipls_agg_accumulate(ipls_agg *h, int p, int target, const void *src, int64_t n,
                         int src_kind);
 
@@ -405,7 +424,9 @@ int ipls_agg_ingest_pubsub(ipls_agg *h, int target, const uint8_t *const *msgs,
  *   blend: target[p][i] = a*target[p][i] + b*g[i]  (products rounded, then the sum)
  *     async replica fold  a = 0.75, b = 1        Updater.java:57-59
  *     leaving-peer blend  a = 0.6,  b = 1 - 0.6  Updater.java:65-69
- *   scale: dst[p][i] = c * src[p][i]             Updater.java:197-199 (0.25 * W) */
+ *   scale: dst[p][i] = c * src[p][i]             Updater.java:197-199 (0.25 * W)
+ * blend also takes HOST_DARR (n = byte length; one partition of a leaving
+ * peer); ipls_agg_load_saved blends a whole saved-model file. */
 int ipls_agg_blend(ipls_agg *h, int p, int target, const void *src, int64_t n, int src_kind,
                    double a, double b);
 int ipls_agg_scale(ipls_agg *h, int p, int dst_target, int src_target, double c);
@@ -454,7 +475,8 @@ int ipls_agg_aggregate_round(ipls_agg *h, int p_first, int n_parts,
  * Weight_Address[p] = GetParameters(hash) -- the downloaded updated partition
  * (n doubles, F64/BE host or device kinds).  src_kind HOST_FRAME (n = frame
  * bytes) is the pid-4 ACK of ThreadReceiver (IPLS.java:491-498): the frame's
- * first L_p payload doubles become Weight_Address[p]. */
+ * first L_p payload doubles become Weight_Address[p].  HOST_DARR (n = byte
+ * length): the serialised double[]'s values, under the GetParameters rule. */
 int ipls_agg_set_weights(ipls_agg *h, int p, const void *src, int64_t n, int src_kind);
 
 /* GetPartitions (IPLS.java:1140-1174): Weights = Weight_Address, then the
@@ -691,6 +713,88 @@ int64_t ipls_agg_commit_partial(ipls_agg *h, int p, int32_t workers, uint8_t *ou
  * first (the reference's ArrayIndexOutOfBoundsException) or out_cap is short. */
 int64_t ipls_agg_merge_files(ipls_agg *h, const uint8_t *const *files, const int64_t *lens, int k,
                              int file_kind, uint8_t *out, int64_t out_cap);
+
+/* ---- saved-model files: Java-serialised weight maps and lists ----
+ * JDK 8 ObjectOutputStream streams that carry whole weight partitions between
+ * peers:
+ *   MAP    HashMap<Integer,double[]> of Weights[p] for p in Auth_List: IPLS.terminate
+ *          -> save_model (IPLS.java:1981-1998, 1904-1911); the peer that takes a
+ *          partition over reads it with DownloadMapParameters (MyIPFSClass.java:
+ *          559-566, IPLS.java:728-731) and the Updater blends it in (Updater.java:65-69)
+ *   DARR   a bare double[]: the single-partition hand-over (MyIPFSClass.java:261-270,
+ *          IPLS.java:136-140)
+ *   DLIST  ArrayList<Double> of the whole model: IPLS_HOST_DLIST above
+ * double[] payloads keep the raw bits of every value; the boxed Doubles of a
+ * DLIST go through Double.doubleToLongBits, so every NaN becomes
+ * 0x7ff8000000000000 (the IPLS_HOST_BE_CANON rule).  Both rules are read from
+ * the JDK 8 sources; no JVM was at hand to pin them.
+ * Entries of a MAP come in java.util.HashMap iteration order (Integer.hashCode()
+ * is the value; table of 16 doubling past 0.75 * capacity). */
+
+/* Host-only codecs (no handle, no GPU), mirrors of ipls_pair_parse / _encode.
+ * Parsers accept exactly the shapes the JDK writes and never read past len;
+ * anything else is IPLS_E_FORMAT with the reason in ipls_agg_last_error(NULL).
+ *
+ * ipls_saved_parse: a MAP.  Returns the entry count and fills the first
+ * min(count, max_entries) rows: key, array length, byte offset of the array's
+ * big-endian payload (any of the three may be NULL).  Duplicate keys are
+ * IPLS_E_FORMAT. */
+int64_t ipls_saved_parse(const uint8_t *bytes, int64_t len, int32_t *keys, int64_t *lens, int64_t *payload_offs,
+                         int64_t max_entries);
+/* The MAP of `n_parts` arrays: keys parts[i] put in that order (a key listed
+ * twice keeps its first position and its first array), arrays[i] of lens[i]
+ * values (g_kind HOST_F64 or HOST_BE).  Returns the byte count; out == NULL:
+ * the count only; IPLS_E_RANGE if out_cap is too small. */
+int64_t ipls_saved_encode(const int32_t *parts, int n_parts, const void *const *arrays, const int64_t *lens, int g_kind,
+                          uint8_t *out, int64_t out_cap);
+/* A DARR: returns the array length, its payload at byte *payload_off (27). */
+int64_t ipls_darr_parse(const uint8_t *bytes, int64_t len, int64_t *payload_off);
+int64_t ipls_darr_encode(const void *g, int64_t n, int g_kind, uint8_t *out, int64_t out_cap);
+/* A DLIST: returns the element count; values (nullable, max_values doubles)
+ * receives the first min(count, max_values) of them after every element
+ * record has been checked. */
+int64_t ipls_dlist_parse(const uint8_t *bytes, int64_t len, double *values, int64_t max_values);
+int64_t ipls_dlist_encode(const void *g, int64_t n, int g_kind, uint8_t *out, int64_t out_cap);
+
+/* save_model (IPLS.java:1904-1911): the MAP of target[p] for p in parts
+ * (Auth_List, in its order; duplicates as ipls_saved_encode), every payload
+ * packed on the device.  target is normally IPLS_TGT_WEIGHTS.  Returns the
+ * byte count; out == NULL: the count only. */
+int64_t ipls_agg_save_model(ipls_agg *h, const int32_t *parts, int n_parts, int target, uint8_t *out, int64_t out_cap);
+
+/* The same file handed to a sink piece by piece, as ONE call: each shard packs
+ * its entries into a staging of this call's own under that shard's lock, every
+ * lock is released before the first sink call, then the pieces -- consecutive,
+ * in stream order, each at most chunk_bytes (>= 16) long -- come back through
+ * the pinned ring.  A non-zero sink return stops the delivery with
+ * IPLS_E_INVAL.  Rules as ipls_agg_finalize_chunked; the sink may call into
+ * the handle.  On a multi-GPU handle the shards are snapshotted one after the
+ * other, and the staging pool is unbounded, as for the other chunked calls. */
+int ipls_agg_save_model_chunked(ipls_agg *h, const int32_t *parts, int n_parts, int target, int64_t chunk_bytes,
+                                IPLS_BYTE_SINK_FN *sink, void *ctx);
+
+/* The DARR file of target[p] (IPLS.java:136-140). */
+int64_t ipls_agg_save_partition(ipls_agg *h, int p, int target, uint8_t *out, int64_t out_cap);
+
+/* The DLIST of target[p][0..L_p) for p = 0..P-1 in order: the loops at
+ * IPLS.java:549-555 and 2255-2260 (count slots included, as there). */
+int64_t ipls_agg_save_model_list(ipls_agg *h, int target, uint8_t *out, int64_t out_cap);
+
+/* DownloadMapParameters plus what the Updater does with the map: for every p
+ * of parts[0..n_parts) (the ChangedList; parts == NULL: every key of the file)
+ *   mode IPLS_SAVED_SET:   target[p][i] = file[p][i]
+ *   mode IPLS_SAVED_BLEND: target[p][i] = a*target[p][i] + b*file[p][i]
+ *        (the leaving-peer blend, a = 0.6, b = 1 - 0.6; ipls_agg_blend's arithmetic)
+ * for i < L_p.  A listed p that the file lacks is IPLS_E_RANGE (Java:
+ * parameters.get(p) == null, then a NullPointerException in the Updater), so
+ * is a file array shorter than L_p (ArrayIndexOutOfBounds, Updater.java:67)
+ * and a key outside [0, P); a longer array contributes its first L_p values.
+ * Everything is validated before the first launch: an error leaves every
+ * target as it was.  The file goes to each GPU once; one launch per shard
+ * decodes the payloads where they lie in it.  *applied (nullable) receives
+ * the number of partitions written. */
+int ipls_agg_load_saved(ipls_agg *h, const uint8_t *bytes, int64_t n, int mode, int target, const int32_t *parts,
+                        int n_parts, double a, double b, int32_t *applied);
 
 #ifdef __cplusplus
 }

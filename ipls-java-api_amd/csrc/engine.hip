@@ -1369,6 +1369,18 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
       be = true;
       break;
     }
+    case IPLS_HOST_DARR: {
+      // the single-partition hand-over file (MyIPFSClass.java:261-270), handled as the Pair's double[]
+      int64_t poff;
+      const char* why = nullptr;
+      const int64_t nd = javaser::parse_darr((const uint8_t*)src, n, &poff, &why);
+      if (nd < 0) return fail(h, IPLS_E_FORMAT, "serialised double[]: %s (ObjectInputStream)", why ? why : "malformed");
+      if (int rc = host_decode_count(src_kind, nd, L, h)) return rc;
+      if (int rc = stage_bucket(h, (const char*)src + poff, (size_t)L * 8, &dptr)) return rc;
+      staged = true;
+      be = true;
+      break;
+    }
     default:
       return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
   }
@@ -1564,14 +1576,14 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
   return rc;
 }
 
-// Hand n values of a stage's device snapshot (complete once st->ready fires)
-// to the sink in chunks of c, with no engine lock held: chunk k + 1 crosses
-// PCIe into one pinned slot on the stage's copy stream while sink() consumes
-// chunk k from the other.  `base` is added to the offsets the sink sees.
-// Releases the stage.
-static int stage_deliver(ipls_dev* h, ipls_stage* st, int64_t n, int64_t c, int64_t base, ipls_chunk_sink sink, void* ctx,
-                  const char* stopped_note) {
-  const double* d = (const double*)st->d;
+// A stage's device snapshot (complete once st->ready fires) handed out in
+// pieces, with no engine lock held: piece k + 1 crosses PCIe into one pinned
+// slot on the stage's copy stream while the consumer has piece k from the
+// other.  The ring itself, in bytes: bytes [0, n) at `d` go to call(host, off,
+// len) in pieces of c bytes; a non-zero return stops it and is returned.  The
+// stage stays the caller's.
+template <class Call>
+static int stage_ring(ipls_dev* h, ipls_stage* st, const char* d, int64_t n, int64_t c, Call call) {
   int rc = IPLS_OK;
   auto try_hip = [&](hipError_t e, const char* what) {
     if (e != hipSuccess && !rc) {
@@ -1592,7 +1604,7 @@ static int stage_deliver(ipls_dev* h, ipls_stage* st, int64_t n, int64_t c, int6
     PinnedSlot& sl = st->slot[k % S];
     const int64_t off = k * c, len = std::min(c, n - off);
     hipStream_t cs = st->copy[k % st->n_copy];
-    try_hip(hipMemcpyAsync(sl.host, d + off, (size_t)len * 8, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
+    try_hip(hipMemcpyAsync(sl.host, d + off, (size_t)len, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
     try_hip(hipEventRecord(sl.ev, cs), "hipEventRecord");
   };
   while (issued < K && issued < S && !rc) issue();   // the ring's first fill
@@ -1601,11 +1613,8 @@ static int stage_deliver(ipls_dev* h, ipls_stage* st, int64_t n, int64_t c, int6
     try_hip(hipEventSynchronize(sl.ev), "hipEventSynchronize");
     if (rc) break;
     const int64_t off = k * c, len = std::min(c, n - off);
-    if (sink(ctx, (const double*)sl.host, base + off, len) != 0)
-      rc = fail_nl(h, IPLS_E_INVAL, "the chunk sink stopped the transfer at offset %lld%s", (long long)(base + off),
-                   stopped_note);
-    else if (issued < K)
-      issue();   // into the slot just consumed
+    if ((rc = call(sl.host, off, len)) != 0) break;
+    if (issued < K) issue();   // into the slot just consumed
   }
   // every copy of this call is done before the stage can be reused (on the
   // success path they already are: each chunk's event was waited for)
@@ -1614,6 +1623,18 @@ static int stage_deliver(ipls_dev* h, ipls_stage* st, int64_t n, int64_t c, int6
     (void)hipGetLastError();
   }
   for (auto& sl : st->slot) sl.pending = false;
+  return rc;
+}
+
+// n values of the snapshot to the sink in chunks of c; `base` is added to the
+// offsets the sink sees.  Releases the stage.
+static int stage_deliver(ipls_dev* h, ipls_stage* st, int64_t n, int64_t c, int64_t base, ipls_chunk_sink sink, void* ctx,
+                  const char* stopped_note) {
+  const int rc = stage_ring(h, st, (const char*)st->d, 8 * n, 8 * c, [&](const void* host, int64_t off, int64_t len) {
+    if (sink(ctx, (const double*)host, base + off / 8, len / 8) == 0) return IPLS_OK;
+    return fail_nl(h, IPLS_E_INVAL, "the chunk sink stopped the transfer at offset %lld%s", (long long)(base + off / 8),
+                   stopped_note);
+  });
   stage_release(h, st);
   return rc;
 }
@@ -1997,6 +2018,15 @@ int dev_set_weights(ipls_dev* h, int p, const void* src, int64_t n, int src_kind
     launch_bswap(h->stream, (const unsigned long long*)h->d_scratch, (unsigned long long*)(h->arena + h->w_off[p]), L);
     HIP_TRY(h, hipGetLastError());
     return IPLS_OK;
+  }
+  if (src_kind == IPLS_HOST_DARR) {   // the array's big-endian payload, then as HOST_BE
+    int64_t poff;
+    const char* why = nullptr;
+    const int64_t nd = javaser::parse_darr((const uint8_t*)src, n, &poff, &why);
+    if (nd < 0) return fail(h, IPLS_E_FORMAT, "serialised double[]: %s (ObjectInputStream)", why ? why : "malformed");
+    src = (const char*)src + poff;
+    n = nd;
+    src_kind = IPLS_HOST_BE;
   }
   // GetParameters(hash, arr) writes data.length/8 values (MyIPFSClass.java:449-452);
   // more than arr.length -> ArrayIndexOutOfBoundsException.
@@ -2677,6 +2707,15 @@ int dev_blend(ipls_dev* h, int p, int target, const void* src, int64_t n, int sr
   if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
   if (!src) return IPLS_OK;
   const int64_t L = h->len[p];
+  if (src_kind == IPLS_HOST_DARR) {   // the array's big-endian payload, then as HOST_BE
+    int64_t poff;
+    const char* why = nullptr;
+    const int64_t nd = javaser::parse_darr((const uint8_t*)src, n, &poff, &why);
+    if (nd < 0) return fail(h, IPLS_E_FORMAT, "serialised double[]: %s (ObjectInputStream)", why ? why : "malformed");
+    src = (const char*)src + poff;
+    n = nd;
+    src_kind = IPLS_HOST_BE;
+  }
   if (n < L) return fail(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n, (long long)L);
   HIP_TRY(h, dev_use(h->device));
   const void* d = src;
@@ -2819,6 +2858,136 @@ int64_t ipls_pair_encode(int32_t workers, const void* g, int64_t n, int g_kind, 
   }
   javaser::write_pair_trailer(out + hl + 8 * n);
   return total;
+}
+
+// ---- saved-model files: host codecs (javaser.hpp) ----
+namespace {
+
+// n doubles (HOST_F64 or HOST_BE) as the big-endian payload of a double[]
+void put_payload(uint8_t* out, const void* g, int64_t n, int g_kind) {
+  if (g_kind == IPLS_HOST_BE) {
+    if (n) std::memcpy(out, g, (size_t)n * 8);
+    return;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    uint64_t v;
+    std::memcpy(&v, (const char*)g + 8 * i, 8);
+    v = __builtin_bswap64(v);
+    std::memcpy(out + 8 * i, &v, 8);
+  }
+}
+
+// Double.doubleToLongBits: every NaN is the canonical one
+uint64_t canon_bits(uint64_t v) {
+  return ((v & 0x7FF0000000000000ull) == 0x7FF0000000000000ull && (v & 0x000FFFFFFFFFFFFFull)) ? 0x7FF8000000000000ull
+                                                                                                : v;
+}
+
+const uint8_t kDlistLead[6] = {0x73, 0x71, 0x00, 0x7E, 0x00, 0x02};   // TC_OBJECT TC_REFERENCE <Double's descriptor>
+
+}  // namespace
+
+int64_t ipls_saved_parse(const uint8_t* bytes, int64_t len, int32_t* keys, int64_t* lens, int64_t* payload_offs,
+                         int64_t max_entries) {
+  if (!bytes || len < 0 || max_entries < 0) return fail(nullptr, IPLS_E_INVAL, "bad argument");
+  const char* why = nullptr;
+  const int64_t n = javaser::parse_saved(bytes, len, keys, lens, payload_offs, max_entries, &why);
+  if (n < 0) return fail(nullptr, IPLS_E_FORMAT, "saved model: %s", why ? why : "malformed");
+  return n;
+}
+
+int64_t ipls_saved_encode(const int32_t* parts, int n_parts, const void* const* arrays, const int64_t* lens, int g_kind,
+                          uint8_t* out, int64_t out_cap) {
+  if (n_parts < 0 || (n_parts > 0 && (!parts || !lens))) return fail(nullptr, IPLS_E_INVAL, "bad argument");
+  if (g_kind != IPLS_HOST_F64 && g_kind != IPLS_HOST_BE) return fail(nullptr, IPLS_E_INVAL, "g_kind must be HOST_F64/BE");
+  std::vector<int32_t> order;
+  int32_t buckets, threshold;
+  javaser::saved_shape(parts, n_parts, order, &buckets, &threshold);
+  // key -> its first listing
+  std::vector<int> at(order.size());
+  for (size_t e = 0; e < order.size(); ++e) at[e] = int(std::find(parts, parts + n_parts, order[e]) - parts);
+  int64_t total = order.empty() ? 82 : 1;
+  for (size_t e = 0; e < order.size(); ++e) {
+    const int64_t L = lens[at[e]];
+    if (L < 0 || L > INT32_MAX || (L > 0 && out && (!arrays || !arrays[at[e]])))
+      return fail(nullptr, IPLS_E_INVAL, "bad array %d", at[e]);
+    total += (e == 0 ? 181 : 20) + 8 * L;
+  }
+  if (!out) return total;
+  if (out_cap < total) return fail(nullptr, IPLS_E_RANGE, "saved model needs %lld bytes", (long long)total);
+  if (order.empty()) return javaser::saved_empty(out);
+  int64_t o = 0;
+  for (size_t e = 0; e < order.size(); ++e) {
+    uint8_t pre[javaser::kSavedPrefixMax];
+    const int64_t L = lens[at[e]];
+    const int64_t pl = javaser::saved_entry_prefix(pre, e == 0, threshold, buckets, (int32_t)order.size(), order[e], (int32_t)L);
+    std::memcpy(out + o, pre, (size_t)pl);
+    put_payload(out + o + pl, arrays ? arrays[at[e]] : nullptr, L, g_kind);
+    o += pl + 8 * L;
+  }
+  out[o++] = 0x78;
+  return o;
+}
+
+int64_t ipls_darr_parse(const uint8_t* bytes, int64_t len, int64_t* payload_off) {
+  if (!bytes || len < 0) return fail(nullptr, IPLS_E_INVAL, "bad argument");
+  const char* why = nullptr;
+  const int64_t n = javaser::parse_darr(bytes, len, payload_off, &why);
+  if (n < 0) return fail(nullptr, IPLS_E_FORMAT, "serialised double[]: %s", why ? why : "malformed");
+  return n;
+}
+
+int64_t ipls_darr_encode(const void* g, int64_t n, int g_kind, uint8_t* out, int64_t out_cap) {
+  if (n < 0 || n > INT32_MAX || (n > 0 && out && !g)) return fail(nullptr, IPLS_E_INVAL, "bad argument");
+  if (g_kind != IPLS_HOST_F64 && g_kind != IPLS_HOST_BE) return fail(nullptr, IPLS_E_INVAL, "g_kind must be HOST_F64/BE");
+  const int64_t total = javaser::kDarrHeader + 8 * n;
+  if (!out) return total;
+  if (out_cap < total) return fail(nullptr, IPLS_E_RANGE, "serialised double[] needs %lld bytes", (long long)total);
+  javaser::darr_header(out, (int32_t)n);
+  put_payload(out + javaser::kDarrHeader, g, n, g_kind);
+  return total;
+}
+
+int64_t ipls_dlist_parse(const uint8_t* bytes, int64_t len, double* values, int64_t max_values) {
+  if (!bytes || len < 0 || max_values < 0) return fail(nullptr, IPLS_E_INVAL, "bad argument");
+  const char* why = nullptr;
+  const int64_t n = javaser::parse_dlist(bytes, len, &why);
+  if (n < 0) return fail(nullptr, IPLS_E_FORMAT, "serialised ArrayList<Double>: %s", why ? why : "malformed");
+  for (int64_t i = 0; i < n; ++i) {
+    const uint8_t* r = bytes + javaser::kDlistFirst + javaser::kDlistRecord * i;
+    if (i > 0 && std::memcmp(r - 6, kDlistLead, 6) != 0)
+      return fail(nullptr, IPLS_E_FORMAT, "serialised ArrayList<Double>: element %lld is not a Double", (long long)i);
+    if (values && i < max_values) {
+      uint64_t v;
+      std::memcpy(&v, r, 8);
+      v = __builtin_bswap64(v);
+      std::memcpy(values + i, &v, 8);
+    }
+  }
+  return n;
+}
+
+int64_t ipls_dlist_encode(const void* g, int64_t n, int g_kind, uint8_t* out, int64_t out_cap) {
+  if (n < 0 || n > INT32_MAX || (n > 0 && out && !g)) return fail(nullptr, IPLS_E_INVAL, "bad argument");
+  if (g_kind != IPLS_HOST_F64 && g_kind != IPLS_HOST_BE) return fail(nullptr, IPLS_E_INVAL, "g_kind must be HOST_F64/BE");
+  const int64_t total = javaser::dlist_total(n);
+  if (!out) return total;
+  if (out_cap < total) return fail(nullptr, IPLS_E_RANGE, "serialised list needs %lld bytes", (long long)total);
+  int64_t o = javaser::dlist_header(out, (int32_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    if (i > 0) {
+      std::memcpy(out + o, kDlistLead, 6);
+      o += 6;
+    }
+    uint64_t v;
+    std::memcpy(&v, (const char*)g + 8 * i, 8);
+    if (g_kind == IPLS_HOST_BE) v = __builtin_bswap64(v);
+    v = __builtin_bswap64(canon_bits(v));
+    std::memcpy(out + o, &v, 8);
+    o += 8;
+  }
+  out[o++] = 0x78;
+  return o;
 }
 
 int64_t dev_commit_partial(ipls_dev* h, int p, int32_t workers, uint8_t* out, int64_t out_cap) {
@@ -3068,6 +3237,152 @@ int64_t dev_publish_many(ipls_dev* h, int n, const int* parts, int target, int32
   for (int i = 0; i < n; ++i)
     HIP_TRY(h, hipMemcpyAsync((unsigned char*)out + offs[i], base + offs[i], (size_t)lens[i], kind, h->stream));
   if (out_kind == IPLS_HOST_TEXT) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return IPLS_OK;
+}
+
+// ---- saved-model files on the device (engine.hpp) ----
+static_assert(sizeof(ser_entry::prefix) == kSerPrefixMax && kSerPrefixMax == javaser::kSavedPrefixMax, "one prefix size");
+
+int dev_ser_pack(ipls_dev* h, const ser_entry* entries, int n, int target, bool boxed, int64_t slot_bytes,
+                 ipls_stage** st_out, int64_t* nbytes) {
+  if (!h || !entries || !st_out || !nbytes || n <= 0 || n > 65535) return fail_nl(h, IPLS_E_INVAL, "bad argument");
+  *st_out = nullptr;
+  std::vector<SerPackJob> jobs((size_t)n);
+  int64_t total = 0, max_words = 1;
+  for (int i = 0; i < n; ++i) {
+    const ser_entry& e = entries[i];
+    if (e.q < 0 || e.q >= h->P) return fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", e.q, h->P);
+    if (target_off(h, e.q, target) < 0) return fail_nl(h, IPLS_E_INVAL, "bad target %d", target);
+    if (e.prefix_len < (boxed ? 6 : 0) || e.prefix_len > kSerPrefixMax) return fail_nl(h, IPLS_E_INVAL, "bad prefix");
+    SerPackJob& j = jobs[(size_t)i];
+    j = SerPackJob{};
+    j.n = h->len[e.q];
+    j.pos = total;
+    j.prefix_len = e.prefix_len;
+    j.suffix = e.suffix;
+    std::memcpy(j.prefix, e.prefix, (size_t)e.prefix_len);
+    const int64_t body = boxed ? 14 * j.n - 6 : 8 * j.n;
+    total += e.prefix_len + body + (e.suffix >= 0 ? 1 : 0);
+    max_words = std::max(max_words, body / 16 + 1);
+  }
+  HIP_TRY_NL(h, dev_use(h->device));
+  ipls_stage* st = nullptr;
+  if (int rc = stage_acquire(h, (size_t)total + 32, (size_t)std::max<int64_t>(16, std::min(slot_bytes, total)), &st))
+    return rc;
+  int rc = IPLS_OK;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    rc = flush_pending(h);
+    for (int i = 0; i < n && !rc; ++i) {
+      const uint8_t* zf = zero_flag(h, entries[i].q, target);
+      jobs[(size_t)i].src =
+          (zf && *zf) ? nullptr : (const unsigned long long*)(h->arena + target_off(h, entries[i].q, target));
+    }
+    void* djobs = nullptr;
+    if (!rc) rc = upload_table(h, jobs.data(), jobs.size() * sizeof(SerPackJob), &djobs);
+    if (!rc) {
+      const dim3 grid(std::max(1u, std::min<unsigned>(blocks_for(max_words, kSerTileWords), 16384)), (unsigned)n);
+      if (boxed) hipLaunchKernelGGL(k_ser_pack_boxed, grid, dim3(kBlock), 0, h->stream, (const SerPackJob*)djobs, (unsigned char*)st->d);
+      else hipLaunchKernelGGL(k_ser_pack, grid, dim3(kBlock), 0, h->stream, (const SerPackJob*)djobs, (unsigned char*)st->d);
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess) e = hipEventRecord(st->ready, h->stream);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(h, IPLS_E_DEVICE, "saved-model pack: %s", hipGetErrorString(e));
+      }
+    }
+  }
+  if (rc) {   // a kernel of this call may have been queued before the failure
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipGetLastError();
+    stage_release(h, st);
+    return rc;
+  }
+  *st_out = st;
+  *nbytes = total;
+  return IPLS_OK;
+}
+
+int dev_ser_deliver(ipls_dev* h, ipls_stage* st, int64_t off, int64_t n, int64_t chunk, int64_t base, ipls_byte_sink sink,
+                    void* ctx) {
+  if (!h || !st || !sink || chunk < 16) return fail_nl(h, IPLS_E_INVAL, "bad argument");
+  HIP_TRY_NL(h, dev_use(h->device));
+  const int64_t c = std::min<int64_t>(chunk, (int64_t)st->slot[0].cap);
+  return stage_ring(h, st, (const char*)st->d + off, n, c, [&](const void* host, int64_t o, int64_t len) {
+    if (sink(ctx, (const uint8_t*)host, base + o, len) == 0) return IPLS_OK;
+    return fail_nl(h, IPLS_E_INVAL, "the byte sink stopped the transfer at offset %lld", (long long)(base + o));
+  });
+}
+
+int dev_ser_apply(ipls_dev* h, const uint8_t* bytes, int64_t lo, int64_t hi, const int* q, const int64_t* offs, int n,
+                  int mode, int target, double a, double b) {
+  if (!h || !bytes || !q || !offs || n <= 0 || n > 65535 || lo < 0 || hi < lo) return fail(h, IPLS_E_INVAL, "bad argument");
+  IPLS_LOCK(h);
+  std::vector<SerApplyJob> jobs((size_t)n);
+  int64_t max_pairs = 1;
+  for (int i = 0; i < n; ++i) {
+    if (int rc = check_part(h, q[i])) return rc;
+    if (target_off(h, q[i], target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
+    const int64_t L = h->len[q[i]];
+    if (offs[i] < lo || offs[i] + 8 * L > hi) return fail(h, IPLS_E_RANGE, "payload of partition %d outside the file", q[i]);
+    jobs[(size_t)i] = SerApplyJob{h->arena + target_off(h, q[i], target), L, offs[i] - lo};
+    max_pairs = std::max(max_pairs, L / 2 + 1);
+  }
+  HIP_TRY(h, dev_use(h->device));
+  if (int rc = ensure_scratch(h, (size_t)(hi - lo) + 32)) return rc;
+  if (int rc = stage_h2d(h, h->d_scratch, bytes + lo, (size_t)(hi - lo))) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (mode == IPLS_SAVED_BLEND) {
+      if (int rc = materialize(h, q[i], target)) return rc;
+    } else if (uint8_t* zf = zero_flag(h, q[i], target)) {
+      *zf = 0;   // every value is written
+    }
+  }
+  void* djobs = nullptr;
+  if (int rc = upload_table(h, jobs.data(), jobs.size() * sizeof(SerApplyJob), &djobs)) return rc;
+  const dim3 grid(std::max(1u, std::min<unsigned>(blocks_for(max_pairs, kSerTileWords), 16384)), (unsigned)n);
+  if (mode == IPLS_SAVED_BLEND)
+    hipLaunchKernelGGL(k_ser_apply<true>, grid, dim3(kBlock), 0, h->stream, (const SerApplyJob*)djobs,
+                       (const unsigned char*)h->d_scratch, a, b);
+  else
+    hipLaunchKernelGGL(k_ser_apply<false>, grid, dim3(kBlock), 0, h->stream, (const SerApplyJob*)djobs,
+                       (const unsigned char*)h->d_scratch, a, b);
+  HIP_TRY(h, hipGetLastError());
+  return IPLS_OK;
+}
+
+int dev_load_dlist(ipls_dev* h, const uint8_t* bytes, int64_t nvals, int64_t hi, bool apply) {
+  if (!h || !bytes) return fail(h, IPLS_E_INVAL, "null argument");
+  IPLS_LOCK(h);
+  const int64_t g0 = h->flat_base;
+  if (hi < 0) hi = h->flat_total;
+  if (hi > nvals || hi < h->flat_total || g0 > hi)
+    return fail(h, IPLS_E_RANGE, "model of %lld values < model size %lld", (long long)nvals, (long long)h->flat_total);
+  HIP_TRY(h, dev_use(h->device));
+  // scratch: [records g0..hi, 14 bytes each, + slack][their values][flag]
+  const int64_t img = 14 * (hi - g0), val_off = align_up(img + 32, 16), flag_off = val_off + 8 * (hi - g0);
+  if (int rc = ensure_scratch(h, (size_t)flag_off + 16)) return rc;
+  unsigned char* base = (unsigned char*)h->d_scratch;
+  unsigned long long* vals = (unsigned long long*)(base + val_off);
+  unsigned* dflag = (unsigned*)(base + flag_off);
+  if (int rc = stage_h2d(h, base, bytes + javaser::kDlistFirst - 6 + 14 * g0, (size_t)img)) return rc;
+  HIP_TRY(h, hipMemsetAsync(dflag, 0, 4, h->stream));
+  hipLaunchKernelGGL(k_ser_unbox, dim3(std::max(1u, std::min<unsigned>(blocks_for(hi - g0, kBlock), 8192))), dim3(kBlock), 0,
+                     h->stream, (const unsigned char*)base, (int64_t)0, g0, hi, vals, dflag);
+  HIP_TRY(h, hipGetLastError());
+  unsigned flag = 0;
+  if (int rc = d2h(h, &flag, dflag, 4)) return rc;
+  if (flag) return fail(h, IPLS_E_FORMAT, "serialised ArrayList<Double>: an element is not a Double");
+  if (!apply) return IPLS_OK;
+  for (int p = 0; p < h->P; ++p) {
+    const int64_t L = h->len[p];
+    // IPLS.java:1883-1895: values for j < min((i+1)c, M), count slot 0.0
+    hipLaunchKernelGGL(k_load_model<false>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, vals,
+                       h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+    HIP_TRY(h, hipGetLastError());
+    h->agg_zero[p] = h->rep_zero[p] = h->fut_zero[p] = 1;   // IPLS.java:1886-1898
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return IPLS_OK;
 }
 

@@ -94,3 +94,33 @@ int64_t dev_publish_many(ipls_dev* h, int n, const int* parts, int target, int32
                          const int64_t* lens, int out_kind);
 int64_t dev_publish(ipls_dev* h, int p, int target, int32_t a, int32_t b, int16_t pid, const uint8_t* origin,
                     int32_t origin_len, void* out, int64_t out_cap, int out_kind);
+
+// ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
+// One run of a file that an engine packs: `prefix` (framing), then engine
+// partition q's values of `target`, then `suffix` (a byte, or -1).
+struct ser_entry {
+  int q;
+  int32_t prefix_len, suffix;
+  unsigned char prefix[192];
+};
+// Pack the entries back to back, in the order given, into a stage of the
+// call's own (pinned slots of slot_bytes) under the engine lock: one launch.
+// boxed: 14-byte Double records (DLIST) instead of a double[] payload.
+// *nbytes is the image's length; hand it out with dev_ser_deliver, then
+// dev_stage_release.
+int dev_ser_pack(ipls_dev* h, const ser_entry* entries, int n, int target, bool boxed, int64_t slot_bytes,
+                 ipls_stage** st, int64_t* nbytes);
+// Image bytes [off, off + n) to the sink in pieces of at most `chunk`, as file
+// bytes base, base + 1, ...; no lock held.  Keeps the stage.
+int dev_ser_deliver(ipls_dev* h, ipls_stage* st, int64_t off, int64_t n, int64_t chunk, int64_t base,
+                    ipls_byte_sink sink, void* ctx);
+// target[q[i]] = or blended with the big-endian payload at file byte offs[i]
+// (validated by the caller: in range, at least L_q values): the file's bytes
+// [lo, hi) go up once, one launch applies every entry.
+int dev_ser_apply(ipls_dev* h, const uint8_t* bytes, int64_t lo, int64_t hi, const int* q, const int64_t* offs, int n,
+                  int mode, int target, double a, double b);
+// InitializeWeights from a DLIST whose header the caller has parsed (nvals
+// elements): the engine decodes and checks records [flat_base, hi) on its GPU
+// (hi < 0: to the end of its own segment),
+// IPLS_E_FORMAT if one is not a Double; with `apply` it then loads its segment.
+int dev_load_dlist(ipls_dev* h, const uint8_t* bytes, int64_t nvals, int64_t hi, bool apply);

@@ -43,6 +43,7 @@
 #include "../../include/ipls_agg.h"
 #include "engine.hpp"
 #include "java_hashmap.hpp"
+#include "javaser.hpp"
 #include "pubsub_host.hpp"
 
 namespace {
@@ -529,6 +530,22 @@ int ipls_agg_last_launch(ipls_agg* H, ipls_launch_info* out) {
 int ipls_agg_load_model(ipls_agg* H, const void* src, int64_t n, int src_kind) {
   KeepDevice keep_device;
   if (!H || !src) return ferr(H, IPLS_E_INVAL, "null argument");
+  if (src_kind == IPLS_HOST_DLIST) {
+    // DownloadParameters' List<Double> (IPLS.java:567): the header here, the
+    // element records on the GPUs -- every shard checks its own (the last one
+    // the elements past the model too) before any shard writes anything
+    const char* why = nullptr;
+    const int64_t nv = ipls::javaser::parse_dlist((const uint8_t*)src, n, &why);
+    if (nv < 0) return ferr(H, IPLS_E_FORMAT, "serialised ArrayList<Double>: %s (ObjectInputStream)", why ? why : "malformed");
+    if (nv < H->flat_total)
+      return ferr(H, IPLS_E_RANGE, "model of %lld values < model size %lld", (long long)nv, (long long)H->flat_total);
+    const std::vector<int> ss = nonempty_shards(H);
+    auto upto = [&](int s) { return s == ss.back() ? nv : (int64_t)-1; };   // -1: the shard's own segment
+    if (ss.size() > 1)
+      if (int rc = par_shards(H, ss, [&](int s) { return dev_load_dlist(H->sh[s], (const uint8_t*)src, nv, upto(s), false); }))
+        return rc;
+    return par_shards(H, ss, [&](int s) { return dev_load_dlist(H->sh[s], (const uint8_t*)src, nv, upto(s), true); });
+  }
   if (H->S() == 1) return fwd(H, 0, dev_load_model(H->sh[0], src, n, src_kind));
   if (n < H->flat_total)
     return ferr(H, IPLS_E_RANGE, "model of %lld values < model size %lld", (long long)n, (long long)H->flat_total);
@@ -1184,6 +1201,235 @@ int64_t ipls_agg_publish_partials(ipls_agg* H, const int32_t* parts, int n_parts
       return fwd(H, s, (int)rc);
   }
   return total;
+}
+
+// ---- saved-model files (javaser.hpp) ----
+namespace {
+
+int64_t entry_bytes(const ipls_agg* H, const ser_entry& e, bool boxed) {
+  const int64_t L = H->len[e.q];
+  return e.prefix_len + (boxed ? 14 * L - 6 : 8 * L) + (e.suffix >= 0 ? 1 : 0);
+}
+
+int64_t stream_bytes(const ipls_agg* H, const std::vector<ser_entry>& ents, bool boxed) {
+  int64_t total = 0;
+  for (const auto& e : ents) total += entry_bytes(H, e, boxed);
+  return total;
+}
+
+// The entries of save_model's map for `parts` (q = handle partition), in
+// HashMap iteration order; none for the empty map.
+int saved_entries(ipls_agg* H, const int32_t* parts, int n_parts, std::vector<ser_entry>& ents) {
+  if (n_parts < 0 || (n_parts > 0 && !parts)) return ferr(H, IPLS_E_INVAL, "bad partition list");
+  for (int i = 0; i < n_parts; ++i)
+    if (!part_ok(H, parts[i])) return range_err(H, parts[i]);
+  std::vector<int32_t> order;
+  int32_t buckets, threshold;
+  ipls::javaser::saved_shape(parts, n_parts, order, &buckets, &threshold);
+  ents.resize(order.size());
+  for (size_t i = 0; i < order.size(); ++i) {
+    ser_entry& e = ents[i];
+    e.q = order[i];
+    if (H->len[e.q] > INT32_MAX) return ferr(H, IPLS_E_RANGE, "partition %d is longer than a Java array", e.q);
+    e.prefix_len = (int32_t)ipls::javaser::saved_entry_prefix(e.prefix, i == 0, threshold, buckets, (int32_t)order.size(),
+                                                             order[i], (int32_t)H->len[e.q]);
+    e.suffix = i + 1 == order.size() ? 0x78 : -1;
+  }
+  return IPLS_OK;
+}
+
+int host_pieces(ipls_agg* H, const uint8_t* b, int64_t n, int64_t chunk, ipls_byte_sink sink, void* ctx) {
+  for (int64_t o = 0; o < n; o += chunk)
+    if (sink(ctx, b + o, o, std::min(chunk, n - o)) != 0)
+      return ferr(H, IPLS_E_INVAL, "the byte sink stopped the transfer at offset %lld", (long long)o);
+  return IPLS_OK;
+}
+
+// Pack the entries (stream order; q = handle partition) on their shards --
+// each shard's run of entries into a staging of this call, under that shard's
+// lock -- then hand the stream to the sink with no lock held, on the calling
+// thread.  Consecutive entries of one shard are adjacent in its image, so the
+// stream is a list of (shard, image range) segments.
+int save_stream(ipls_agg* H, const std::vector<ser_entry>& ents, bool boxed, int target, int64_t chunk,
+                ipls_byte_sink sink, void* ctx) {
+  struct Seg {
+    int s;
+    int64_t off, len, base;
+  };
+  std::vector<std::vector<ser_entry>> per(H->S());
+  std::vector<int64_t> fill(H->S(), 0);
+  std::vector<Seg> segs;
+  int64_t base = 0;
+  for (const auto& g : ents) {
+    const int s = H->owner[g.q];
+    const int64_t nb = entry_bytes(H, g, boxed);
+    if (!segs.empty() && segs.back().s == s) segs.back().len += nb;
+    else segs.push_back(Seg{s, fill[s], nb, base});
+    ser_entry e = g;
+    e.q = g.q - H->lo[s];
+    per[s].push_back(e);
+    fill[s] += nb;
+    base += nb;
+  }
+  std::vector<ipls_stage*> st(H->S(), nullptr);
+  int rc = IPLS_OK;
+  for (int s = 0; s < H->S() && !rc; ++s) {
+    if (per[s].empty()) continue;
+    int64_t nb = 0;
+    H->last_shard.store(s, std::memory_order_relaxed);
+    rc = fwd(H, s, dev_ser_pack(H->sh[s], per[s].data(), (int)per[s].size(), target, boxed, chunk, &st[s], &nb));
+  }
+  for (size_t i = 0; i < segs.size() && !rc; ++i) {
+    const Seg& g = segs[i];
+    rc = fwd(H, g.s, dev_ser_deliver(H->sh[g.s], st[g.s], g.off, g.len, chunk, g.base, sink, ctx));
+  }
+  for (int s = 0; s < H->S(); ++s)
+    if (st[s]) dev_stage_release(H->sh[s], st[s]);
+  return rc;
+}
+
+struct CopySink {
+  uint8_t* out;
+  static int put(void* ctx, const uint8_t* bytes, int64_t offset, int64_t n) {
+    std::memcpy(((CopySink*)ctx)->out + offset, bytes, (size_t)n);
+    return 0;
+  }
+};
+constexpr int64_t kSaveChunk = 4 << 20;   // pieces of the one-buffer calls
+
+// out == NULL: the size; else the whole stream into out
+int64_t save_to(ipls_agg* H, const std::vector<ser_entry>& ents, bool boxed, int target, uint8_t* out, int64_t out_cap) {
+  const int64_t total = stream_bytes(H, ents, boxed);
+  if (!out) return total;
+  if (out_cap < total) return ferr(H, IPLS_E_RANGE, "the file needs %lld bytes", (long long)total);
+  CopySink cs{out};
+  if (int rc = save_stream(H, ents, boxed, target, kSaveChunk, CopySink::put, &cs)) return rc;
+  return total;
+}
+
+bool target_ok(int target) { return target >= IPLS_TGT_AGG && target <= IPLS_TGT_FUTURE; }
+
+}  // namespace
+
+int ipls_agg_save_model_chunked(ipls_agg* H, const int32_t* parts, int n_parts, int target, int64_t chunk_bytes,
+                                IPLS_BYTE_SINK_FN* sink, void* ctx) {
+  KeepDevice keep_device;
+  if (!H || !sink) return ferr(H, IPLS_E_INVAL, "null argument");
+  if (chunk_bytes < 16) return ferr(H, IPLS_E_INVAL, "chunk of %lld bytes: at least 16", (long long)chunk_bytes);
+  if (!target_ok(target)) return ferr(H, IPLS_E_INVAL, "bad target %d", target);
+  std::vector<ser_entry> ents;
+  if (int rc = saved_entries(H, parts, n_parts, ents)) return rc;
+  if (ents.empty()) {
+    uint8_t b[ipls::javaser::kSavedPrefixMax];
+    return host_pieces(H, b, ipls::javaser::saved_empty(b), chunk_bytes, sink, ctx);
+  }
+  return save_stream(H, ents, false, target, chunk_bytes, sink, ctx);
+}
+
+int64_t ipls_agg_save_model(ipls_agg* H, const int32_t* parts, int n_parts, int target, uint8_t* out, int64_t out_cap) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (!target_ok(target)) return ferr(H, IPLS_E_INVAL, "bad target %d", target);
+  std::vector<ser_entry> ents;
+  if (int rc = saved_entries(H, parts, n_parts, ents)) return rc;
+  if (ents.empty()) {
+    if (!out) return 82;
+    if (out_cap < 82) return ferr(H, IPLS_E_RANGE, "the file needs 82 bytes");
+    return ipls::javaser::saved_empty(out);
+  }
+  return save_to(H, ents, false, target, out, out_cap);
+}
+
+int64_t ipls_agg_save_partition(ipls_agg* H, int p, int target, uint8_t* out, int64_t out_cap) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (!part_ok(H, p)) return range_err(H, p);
+  if (!target_ok(target)) return ferr(H, IPLS_E_INVAL, "bad target %d", target);
+  if (H->len[p] > INT32_MAX) return ferr(H, IPLS_E_RANGE, "partition %d is longer than a Java array", p);
+  std::vector<ser_entry> ents(1);
+  ents[0].q = p;
+  ents[0].prefix_len = (int32_t)ipls::javaser::darr_header(ents[0].prefix, (int32_t)H->len[p]);
+  ents[0].suffix = -1;
+  return save_to(H, ents, false, target, out, out_cap);
+}
+
+int64_t ipls_agg_save_model_list(ipls_agg* H, int target, uint8_t* out, int64_t out_cap) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (!target_ok(target)) return ferr(H, IPLS_E_INVAL, "bad target %d", target);
+  int64_t n = 0;
+  for (int p = 0; p < H->P; ++p) n += H->len[p];
+  if (n > INT32_MAX) return ferr(H, IPLS_E_RANGE, "a model of %lld values is longer than a Java list", (long long)n);
+  std::vector<ser_entry> ents((size_t)H->P);
+  static const unsigned char lead[6] = {0x73, 0x71, 0x00, 0x7E, 0x00, 0x02};   // a later Double: its class by reference
+  for (int p = 0; p < H->P; ++p) {
+    ser_entry& e = ents[(size_t)p];
+    e.q = p;
+    if (p == 0) {
+      e.prefix_len = (int32_t)ipls::javaser::dlist_header(e.prefix, (int32_t)n);
+    } else {
+      std::memcpy(e.prefix, lead, 6);
+      e.prefix_len = 6;
+    }
+    e.suffix = p + 1 == H->P ? 0x78 : -1;
+  }
+  return save_to(H, ents, true, target, out, out_cap);
+}
+
+int ipls_agg_load_saved(ipls_agg* H, const uint8_t* bytes, int64_t n, int mode, int target, const int32_t* parts,
+                        int n_parts, double a, double b, int32_t* applied) {
+  KeepDevice keep_device;
+  if (!H || !bytes) return ferr(H, IPLS_E_INVAL, "null argument");
+  if (mode != IPLS_SAVED_SET && mode != IPLS_SAVED_BLEND) return ferr(H, IPLS_E_INVAL, "bad mode %d", mode);
+  if (!target_ok(target)) return ferr(H, IPLS_E_INVAL, "bad target %d", target);
+  if (parts && n_parts < 0) return ferr(H, IPLS_E_INVAL, "bad partition list");
+  const char* why = nullptr;
+  const int64_t cnt = ipls::javaser::parse_saved(bytes, n, nullptr, nullptr, nullptr, 0, &why);
+  if (cnt < 0) return ferr(H, IPLS_E_FORMAT, "saved model: %s (ObjectInputStream)", why ? why : "malformed");
+  std::vector<int32_t> keys((size_t)cnt);
+  std::vector<int64_t> lens((size_t)cnt), offs((size_t)cnt);
+  ipls::javaser::parse_saved(bytes, n, keys.data(), lens.data(), offs.data(), cnt, &why);
+  // what to apply: the ChangedList, or every key of the file
+  std::vector<int32_t> want;
+  if (parts) want.assign(parts, parts + n_parts);
+  else want = keys;
+  std::vector<std::vector<int>> q(H->S());
+  std::vector<std::vector<int64_t>> po(H->S());
+  std::vector<char> seen((size_t)H->P, 0);
+  for (int32_t p : want) {
+    if (!part_ok(H, p)) return range_err(H, p);
+    if (seen[(size_t)p]) continue;   // a partition listed twice is applied once
+    seen[(size_t)p] = 1;
+    const auto it = std::find(keys.begin(), keys.end(), p);
+    if (it == keys.end())
+      return ferr(H, IPLS_E_RANGE, "the saved model has no partition %d (NullPointerException, Updater.java:67)", p);
+    const size_t e = size_t(it - keys.begin());
+    if (lens[e] < H->len[p])
+      return ferr(H, IPLS_E_RANGE, "saved partition %d of %lld doubles shorter than partition length %lld "
+                  "(ArrayIndexOutOfBoundsException, Updater.java:67)", p, (long long)lens[e], (long long)H->len[p]);
+    const int s = H->owner[p];
+    q[s].push_back(p - H->lo[s]);
+    po[s].push_back(offs[e]);
+  }
+  std::vector<int> ss;
+  int32_t total = 0;
+  for (int s = 0; s < H->S(); ++s)
+    if (!q[s].empty()) {
+      ss.push_back(s);
+      total += (int32_t)q[s].size();
+    }
+  if (applied) *applied = 0;
+  const int rc = par_shards(H, ss, [&](int s) {
+    // this shard's slice of the file: from its first payload to the end of its last
+    int64_t lo = n, hi = 0;
+    for (size_t i = 0; i < q[s].size(); ++i) {
+      lo = std::min(lo, po[s][i]);
+      hi = std::max(hi, po[s][i] + 8 * H->len[H->lo[s] + q[s][i]]);
+    }
+    return dev_ser_apply(H->sh[s], bytes, lo, hi, q[s].data(), po[s].data(), (int)q[s].size(), mode, target, a, b);
+  });
+  if (!rc && applied) *applied = total;
+  return rc;
 }
 
 // ---- replica slots across GPUs ----

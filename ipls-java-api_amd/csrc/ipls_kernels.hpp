@@ -1267,4 +1267,236 @@ __global__ __launch_bounds__(kBlock) void k_encode_secure(const unsigned long lo
   }
 }
 
+// ---------------------------------------------------------------------------
+// Saved-model files (javaser.hpp): Java object streams whose double payloads
+// sit at byte offsets that are never 8-B aligned (MAP 5 or 1 mod 8, DARR 27,
+// DLIST odd offsets in a 14-byte stride).  An image is the file's bytes (or a
+// contiguous piece of them) in a 16-B aligned device buffer; a job is one run
+// of framing + payload inside it.  blockIdx.y = job.
+//
+// Pack: the image's aligned 16-B words that lie wholly inside a payload are
+// each written once, by one non-temporal 16-B store composed in registers
+// from the neighbouring values (a funnel shift by the job's byte residue);
+// the bytes before the first and after the last such word of a job -- its
+// framing, under 16 payload bytes each side, the suffix -- are written one
+// byte at a time by the job's first block.  No byte has two writers, and a
+// 16-B word that two jobs share is byte-written by both (disjoint bytes).
+// ---------------------------------------------------------------------------
+constexpr int kSerV = 4;                                       // 16-B words per lane per tile
+constexpr int64_t kSerTileWords = (int64_t)kBlock * kSerV;     // 16 KiB of image per block
+constexpr int kSerPrefixMax = 192;
+
+struct SerPackJob {
+  const unsigned long long* src;   // n native doubles, or null = logically +0.0
+  int64_t n;
+  int64_t pos;                     // image byte offset of the job's first byte
+  int32_t prefix_len;
+  int32_t suffix;                  // one byte after the payload, or -1
+  unsigned char prefix[kSerPrefixMax];
+};
+
+// X = the 8 stream bytes that start s bytes (0..7) into the big-endian
+// sequence hi, lo -- as a big-endian integer
+__device__ __forceinline__ unsigned long long ser_funnel(unsigned long long hi, unsigned long long lo, int s) {
+  return s ? (hi << (8 * s)) | (lo >> (64 - 8 * s)) : hi;
+}
+
+__device__ __forceinline__ unsigned ser_pack_byte(const SerPackJob& j, int64_t B, int64_t E, int64_t a) {
+  if (a < B) return j.prefix[a - j.pos];
+  if (a >= E) return (unsigned)j.suffix;
+  if (!j.src) return 0;
+  const int64_t q = a - B;
+  return (unsigned)(ld8(j.src + (q >> 3)) >> (8 * (7 - (q & 7)))) & 0xFF;
+}
+
+__global__ __launch_bounds__(kBlock) void k_ser_pack(const SerPackJob* __restrict__ jobs, unsigned char* __restrict__ img) {
+  const SerPackJob& j = jobs[blockIdx.y];
+  const int64_t B = j.pos + j.prefix_len, E = B + 8 * j.n;     // the payload's bytes
+  const int64_t end = E + (j.suffix >= 0 ? 1 : 0);
+  int64_t w0 = (B + 15) >> 4, w1 = E >> 4;                      // whole words [w0, w1)
+  if (w1 < w0) w1 = w0;
+  const int s = (int)((16 * w0 - B) & 7);                       // bytes into value k where a word starts
+  const unsigned long long* src = j.src;
+  // word w starts in value k = (16 w - B) >> 3 and needs values k, k + 1 and (s > 0) k + 2 < n
+  auto compose = [&](unsigned long long a, unsigned long long b, unsigned long long c) {
+    return u2{__builtin_bswap64(ser_funnel(a, b, s)), __builtin_bswap64(ser_funnel(b, c, s))};
+  };
+  for (int64_t t0 = w0 + (int64_t)blockIdx.x * kSerTileWords; t0 < w1; t0 += (int64_t)gridDim.x * kSerTileWords) {
+    if (!src) {
+#pragma unroll
+      for (int v = 0; v < kSerV; ++v) {
+        const int64_t w = t0 + (int64_t)v * kBlock + threadIdx.x;
+        if (w < w1) __builtin_nontemporal_store(u2{0, 0}, (gu2)(img + 16 * w));
+      }
+      continue;
+    }
+    unsigned long long a[kSerV], b[kSerV], c[kSerV];
+#pragma unroll
+    for (int v = 0; v < kSerV; ++v) {
+      const int64_t w = t0 + (int64_t)v * kBlock + threadIdx.x;
+      a[v] = b[v] = c[v] = 0;
+      if (w < w1) {
+        const int64_t k = (16 * w - B) >> 3;
+        a[v] = ld8(src + k);
+        b[v] = ld8(src + k + 1);
+        if (s) c[v] = ld8(src + k + 2);
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kSerV; ++v) {
+      const int64_t w = t0 + (int64_t)v * kBlock + threadIdx.x;
+      if (w < w1) __builtin_nontemporal_store(compose(a[v], b[v], c[v]), (gu2)(img + 16 * w));
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int64_t head_end = w1 > w0 ? 16 * w0 : end;           // no whole word: everything byte-wise
+    for (int64_t a = j.pos + threadIdx.x; a < head_end; a += kBlock) img[a] = (unsigned char)ser_pack_byte(j, B, E, a);
+    if (w1 > w0)
+      for (int64_t a = 16 * w1 + threadIdx.x; a < end; a += kBlock) img[a] = (unsigned char)ser_pack_byte(j, B, E, a);
+  }
+}
+
+// Boxed pack (DLIST): after the job's prefix come n records of 14 bytes whose
+// first six are constant, except that the first record's six are the last six
+// bytes of the prefix -- so the record region starts at B = pos + prefix_len
+// - 6 and value g sits at B + 14 g + 6.  A 16-B word touches at most two
+// values and the first lead byte of a third record.  Values are
+// doubleToLongBits: NaN canonicalised.
+constexpr unsigned long long kBoxLead = 0x7371007E0002ull;      // TC_OBJECT TC_REFERENCE 0x7e0002, 48 bits
+
+__device__ __forceinline__ unsigned long long canon_nan_bits(unsigned long long v) {
+  return ((v & 0x7FF0000000000000ull) == 0x7FF0000000000000ull && (v & 0x000FFFFFFFFFFFFFull)) ? 0x7FF8000000000000ull : v;
+}
+
+__device__ __forceinline__ unsigned ser_box_byte(const SerPackJob& j, int64_t B, int64_t E, int64_t a) {
+  if (a < B + 6) return j.prefix[a - j.pos];
+  if (a >= E) return (unsigned)j.suffix;
+  const int64_t t = a - B, g = t / 14;
+  const int o = (int)(t - 14 * g);
+  if (o < 6) return (unsigned)(kBoxLead >> (8 * (5 - o))) & 0xFF;
+  const unsigned long long v = j.src ? canon_nan_bits(ld8(j.src + g)) : 0;
+  return (unsigned)(v >> (8 * (13 - o))) & 0xFF;
+}
+
+__global__ __launch_bounds__(kBlock) void k_ser_pack_boxed(const SerPackJob* __restrict__ jobs,
+                                                           unsigned char* __restrict__ img) {
+  const SerPackJob& j = jobs[blockIdx.y];
+  const int64_t B = j.pos + j.prefix_len - 6, E = B + 14 * j.n;   // records [B, E)
+  const int64_t end = E + (j.suffix >= 0 ? 1 : 0);
+  int64_t w0 = (B + 6 + 15) >> 4, w1 = E >> 4;                    // whole words past the prefix
+  if (w1 < w0) w1 = w0;
+  const unsigned long long* src = j.src;
+  for (int64_t t0 = w0 + (int64_t)blockIdx.x * kSerTileWords; t0 < w1; t0 += (int64_t)gridDim.x * kSerTileWords) {
+#pragma unroll
+    for (int v = 0; v < kSerV; ++v) {
+      const int64_t w = t0 + (int64_t)v * kBlock + threadIdx.x;
+      if (w >= w1) continue;
+      const int64_t t = 16 * w - B, g = t / 14;
+      const int o = (int)(t - 14 * g);                              // 0..13: where the word starts in record g
+      // record g + 1 exists whenever the word reaches its value (o > 4)
+      unsigned long long x = 0, y = 0;
+      if (src) {
+        x = canon_nan_bits(ld8(src + g));
+        if (o > 4) y = canon_nan_bits(ld8(src + g + 1));
+      }
+      // the 32 stream bytes from record g's start, as big-endian words
+      const unsigned long long q0 = (kBoxLead << 16) | (x >> 48), q1 = (x << 16) | (kBoxLead >> 32),
+                               q2 = (kBoxLead << 32) | (y >> 32), q3 = (y << 32) | (kBoxLead >> 16);
+      const int sh = o & 7;
+      const unsigned long long lo = o < 8 ? q0 : q1, mid = o < 8 ? q1 : q2, hi = o < 8 ? q2 : q3;
+      __builtin_nontemporal_store(u2{__builtin_bswap64(ser_funnel(lo, mid, sh)), __builtin_bswap64(ser_funnel(mid, hi, sh))},
+                                  (gu2)(img + 16 * w));
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int64_t head_end = w1 > w0 ? 16 * w0 : end;
+    for (int64_t a = j.pos + threadIdx.x; a < head_end; a += kBlock) img[a] = (unsigned char)ser_box_byte(j, B, E, a);
+    if (w1 > w0)
+      for (int64_t a = 16 * w1 + threadIdx.x; a < end; a += kBlock) img[a] = (unsigned char)ser_box_byte(j, B, E, a);
+  }
+}
+
+// Unpack and apply: target[i] = v[i] (SET) or a*target[i] + b*v[i] (BLEND:
+// k_blend's arithmetic, both products rounded, then the sum), v[i] the
+// big-endian double at image byte off + 8 i, any residue.  The image buffer is
+// readable for 32 bytes past its last payload byte.
+struct SerApplyJob {
+  double* dst;
+  int64_t n;
+  int64_t off;                     // image byte offset of the payload
+};
+
+// the 8 image bytes at byte a, as the value they encode (two aligned 8-B loads)
+__device__ __forceinline__ unsigned long long ser_load_be(const unsigned char* img, int64_t a) {
+  const unsigned long long* w = (const unsigned long long*)(img + (a & ~(int64_t)7));
+  const int r = (int)(a & 7);
+  const unsigned long long m0 = ld8(w);
+  if (!r) return __builtin_bswap64(m0);
+  return __builtin_bswap64((m0 >> (8 * r)) | (ld8(w + 1) << (64 - 8 * r)));
+}
+
+template <bool BLEND>
+__global__ __launch_bounds__(kBlock) void k_ser_apply(const SerApplyJob* __restrict__ jobs,
+                                                      const unsigned char* __restrict__ img, double a, double b) {
+  const SerApplyJob& j = jobs[blockIdx.y];
+  double* dst = j.dst;
+  auto put = [&](double t, unsigned long long bits) {
+    const double x = __builtin_bit_cast(double, bits);
+    if constexpr (BLEND) {
+      const double aw = a * t, bg = b * x;
+      return aw + bg;
+    } else {
+      return x;
+    }
+  };
+  const bool vec = (((uintptr_t)dst) & 15) == 0;
+  const int64_t pairs = vec ? j.n >> 1 : 0;
+  const int r = (int)(j.off & 15), rr = r & 7;                    // the same for every pair of the job
+  for (int64_t t0 = (int64_t)blockIdx.x * kSerTileWords; t0 < pairs; t0 += (int64_t)gridDim.x * kSerTileWords) {
+    u2 m0[kSerV], m1[kSerV], tv[kSerV];
+#pragma unroll
+    for (int v = 0; v < kSerV; ++v) {
+      const int64_t i = t0 + (int64_t)v * kBlock + threadIdx.x;
+      if (i < pairs) {
+        const unsigned long long* w = (const unsigned long long*)(img + ((j.off + 16 * i) & ~(int64_t)15));
+        m0[v] = __builtin_nontemporal_load((gcu2)w);
+        m1[v] = r ? *(gcu2)(w + 2) : u2{0, 0};
+        if constexpr (BLEND) tv[v] = *(gcu2)(dst + 2 * i);
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kSerV; ++v) {
+      const int64_t i = t0 + (int64_t)v * kBlock + threadIdx.x;
+      if (i < pairs) {
+        // the 32 image bytes from the aligned word, as little-endian words
+        const unsigned long long a0 = m0[v].x, a1 = m0[v].y, a2 = m1[v].x, a3 = m1[v].y;
+        const unsigned long long l0 = r < 8 ? a0 : a1, l1 = r < 8 ? a1 : a2, l2 = r < 8 ? a2 : a3;
+        const unsigned long long e0 = rr ? (l0 >> (8 * rr)) | (l1 << (64 - 8 * rr)) : l0;
+        const unsigned long long e1 = rr ? (l1 >> (8 * rr)) | (l2 << (64 - 8 * rr)) : l1;
+        d2 t = d2{0.0, 0.0};
+        if constexpr (BLEND) t = __builtin_bit_cast(d2, tv[v]);
+        const double ox = put(t.x, __builtin_bswap64(e0)), oy = put(t.y, __builtin_bswap64(e1));
+        *(gu2)(dst + 2 * i) = __builtin_bit_cast(u2, d2{ox, oy});
+      }
+    }
+  }
+  // the odd last value, or every value of a target that is not 16-B aligned
+  for (int64_t i = 2 * pairs + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < j.n; i += (int64_t)gridDim.x * kBlock)
+    dst[i] = put(BLEND ? dst[i] : 0.0, ser_load_be(img, j.off + 8 * i));
+}
+
+// Unpack, boxed (DLIST): out[g - g0] = value g for g in [g0, g1) of the
+// records at image byte rec0 + 14 g (six lead bytes, eight value bytes); a
+// record g >= 1 whose lead is not the constant sets *flag.  The host checks
+// the flag before anything is applied.
+__global__ __launch_bounds__(kBlock) void k_ser_unbox(const unsigned char* __restrict__ img, int64_t rec0, int64_t g0,
+                                                      int64_t g1, unsigned long long* __restrict__ out,
+                                                      unsigned* __restrict__ flag) {
+  for (int64_t g = g0 + (int64_t)blockIdx.x * kBlock + threadIdx.x; g < g1; g += (int64_t)gridDim.x * kBlock) {
+    const int64_t a = rec0 + 14 * (g - g0);
+    if (g >= 1 && (ser_load_be(img, a) >> 16) != kBoxLead) *flag = 1u;
+    out[g - g0] = ser_load_be(img, a + 6);
+  }
+}
+
 }  // namespace ipls

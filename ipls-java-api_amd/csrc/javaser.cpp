@@ -2,12 +2,17 @@
 // Serialization Specification's (magic, TC_* tags, class descriptors,
 // handles from 0x7e0000); the serialVersionUIDs are the ones in the files the
 // reference wrote itself (its Scheduler file: org.javatuples.Pair/Tuple,
-// Object[], Integer, Number, Arrays$ArrayList; ETHModel: [D).
+// Object[], Integer, Number, Arrays$ArrayList; ETHModel: [D; Uniform/Node1:
+// ArrayList, Double).  java.util.HashMap's is the JDK 8 source's: no file of
+// the reference holds one.
 #include "javaser.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "java_hashmap.hpp"
 
 namespace ipls {
 namespace javaser {
@@ -22,7 +27,8 @@ constexpr int32_t kBaseHandle = 0x7E0000;
 constexpr uint64_t kSuidPair = 0x21D5DEE583774BBAull, kSuidTuple = 0x4B5F179B83A89E3Dull,
                    kSuidObjArray = 0x90CE589F1073296Cull, kSuidInteger = 0x12E2A0A4F7818738ull,
                    kSuidNumber = 0x86AC951D0B94E08Bull, kSuidArraysList = 0xD9A43CBECD8806D2ull,
-                   kSuidDoubleArray = 0x3EA68C14AB635A1Eull;
+                   kSuidDoubleArray = 0x3EA68C14AB635A1Eull, kSuidHashMap = 0x0507DAC1C31660D1ull,
+                   kSuidArrayList = 0x7881D21D99C7619Dull, kSuidDouble = 0x80B3C24A296BFB04ull;
 
 // ---- writer ---------------------------------------------------------------
 struct Writer {
@@ -48,10 +54,10 @@ struct Writer {
   int32_t handle() { return next++; }
   void ref(int32_t h) { u8(TC_REFERENCE), i32(h); }
   // TC_CLASSDESC name suid; the descriptor's handle is assigned here
-  int32_t desc(const char* name, uint64_t suid) {
+  int32_t desc(const char* name, uint64_t suid, uint8_t flags = SC_SERIALIZABLE) {
     u8(TC_CLASSDESC), utf(name), u64(suid);
     const int32_t h = handle();
-    u8(SC_SERIALIZABLE);
+    u8(flags);
     return h;
   }
 };
@@ -419,6 +425,226 @@ int64_t parse_pair(const uint8_t* buf, int64_t n, int32_t* workers, int64_t* pay
   if (workers) *workers = int32_t(iv->v);
   if (payload_off) *payload_off = g.off;
   return g.len;
+}
+
+// ---- saved-model files: HashMap<Integer,double[]>, double[], ArrayList<Double> ----
+namespace {
+
+// stream header of the map up to and including the block data (buckets, size)
+void emit_map_header(Writer& w, int32_t threshold, int32_t buckets, int32_t size) {
+  w.u8(0xAC), w.u8(0xED), w.u16(5);
+  w.u8(TC_OBJECT);
+  w.desc("java.util.HashMap", kSuidHashMap, SC_SERIALIZABLE | SC_WRITE_METHOD);
+  w.u16(2), w.u8('F'), w.utf("loadFactor"), w.u8('I'), w.utf("threshold");
+  w.u8(TC_ENDBLOCKDATA), w.u8(TC_NULL);
+  w.handle();                       // the map: 0x7e0001
+  w.i32(0x3F400000), w.i32(threshold);
+  w.u8(TC_BLOCKDATA), w.u8(8), w.i32(buckets), w.i32(size);
+}
+
+// key and array header of entry `first ? 0 : later`; the payload follows
+void emit_map_entry(Writer& w, bool first, int32_t key, int32_t len) {
+  w.u8(TC_OBJECT);
+  if (first) {
+    w.desc("java.lang.Integer", kSuidInteger);                    // 0x7e0002
+    w.u16(1), w.u8('I'), w.utf("value"), w.u8(TC_ENDBLOCKDATA);
+    w.desc("java.lang.Number", kSuidNumber);                      // 0x7e0003
+    w.u16(0), w.u8(TC_ENDBLOCKDATA), w.u8(TC_NULL);
+  } else {
+    w.ref(kBaseHandle + 2);
+  }
+  w.i32(key);
+  w.u8(TC_ARRAY);
+  if (first) {
+    w.desc("[D", kSuidDoubleArray);                               // 0x7e0005
+    w.u16(0), w.u8(TC_ENDBLOCKDATA), w.u8(TC_NULL);
+  } else {
+    w.ref(kBaseHandle + 5);
+  }
+  w.i32(len);
+}
+
+void emit_darr_header(Writer& w, int32_t len) {
+  w.u8(0xAC), w.u8(0xED), w.u16(5);
+  w.u8(TC_ARRAY);
+  w.desc("[D", kSuidDoubleArray);
+  w.u16(0), w.u8(TC_ENDBLOCKDATA), w.u8(TC_NULL);
+  w.i32(len);
+}
+
+// ArrayList.writeObject: the size field, the size again as block data, then
+// the elements; the first Double carries its two class descriptors
+void emit_dlist_header(Writer& w, int32_t n) {
+  w.u8(0xAC), w.u8(0xED), w.u16(5);
+  w.u8(TC_OBJECT);
+  w.desc("java.util.ArrayList", kSuidArrayList, SC_SERIALIZABLE | SC_WRITE_METHOD);   // 0x7e0000
+  w.u16(1), w.u8('I'), w.utf("size"), w.u8(TC_ENDBLOCKDATA), w.u8(TC_NULL);
+  w.i32(n);
+  w.u8(TC_BLOCKDATA), w.u8(4), w.i32(n);
+  if (n == 0) return;
+  w.u8(TC_OBJECT);
+  w.desc("java.lang.Double", kSuidDouble);                                            // 0x7e0002
+  w.u16(1), w.u8('D'), w.utf("value"), w.u8(TC_ENDBLOCKDATA);
+  w.desc("java.lang.Number", kSuidNumber);
+  w.u16(0), w.u8(TC_ENDBLOCKDATA), w.u8(TC_NULL);
+}
+
+// A bounded cursor over the stream that accepts exact bytes only.
+struct Cursor {
+  const uint8_t* b;
+  int64_t n, i = 0;
+  const char* why = nullptr;
+  bool fail(const char* w) {
+    if (!why) why = w;
+    return false;
+  }
+  bool expect(const uint8_t* want, int64_t k, const char* what) {
+    if (k > n - i) return fail("truncated stream");
+    if (std::memcmp(b + i, want, (size_t)k) != 0) return fail(what);
+    i += k;
+    return true;
+  }
+  bool i32(int32_t& v) {
+    if (4 > n - i) return fail("truncated stream");
+    v = int32_t(uint32_t(b[i]) << 24 | uint32_t(b[i + 1]) << 16 | uint32_t(b[i + 2]) << 8 | uint32_t(b[i + 3]));
+    i += 4;
+    return true;
+  }
+};
+
+}  // namespace
+
+void saved_shape(const int32_t* parts, int n_parts, std::vector<int32_t>& order, int32_t* buckets, int32_t* threshold) {
+  JavaHashOrder map;   // Integer.hashCode() == value
+  for (int i = 0; i < n_parts; ++i)
+    if (!map.contains({parts[i], 0})) map.put_new({parts[i], 0}, parts[i]);
+  order.clear();
+  for (const auto& k : map.order()) order.push_back(k.first);
+  // HashMap.writeObject: capacity() is 16 for a table never allocated, whose threshold is 0
+  *buckets = map.capacity() ? (int32_t)map.capacity() : 16;
+  *threshold = (int32_t)(map.capacity() / 4 * 3);
+}
+
+int64_t saved_entry_prefix(uint8_t* out, bool first, int32_t threshold, int32_t buckets, int32_t size, int32_t key,
+                           int32_t len) {
+  Writer w{out};
+  if (first) emit_map_header(w, threshold, buckets, size);
+  emit_map_entry(w, first, key, len);
+  return w.n;
+}
+
+int64_t saved_empty(uint8_t* out) {
+  Writer w{out};
+  emit_map_header(w, 0, 16, 0);
+  w.u8(TC_ENDBLOCKDATA);
+  return w.n;
+}
+
+int64_t darr_header(uint8_t* out, int32_t len) {
+  Writer w{out};
+  emit_darr_header(w, len);
+  return w.n;
+}
+
+int64_t dlist_header(uint8_t* out, int32_t n) {
+  Writer w{out};
+  emit_dlist_header(w, n);
+  return w.n;
+}
+
+int64_t dlist_total(int64_t n) { return n == 0 ? 58 : kDlistFirst + 8 + kDlistRecord * (n - 1) + 1; }
+
+int64_t parse_saved(const uint8_t* buf, int64_t n, int32_t* keys, int64_t* lens, int64_t* offs, int64_t max_entries,
+                    const char** why) {
+  Cursor c{buf, n};
+  auto bad = [&](const char* w) -> int64_t {
+    if (why) *why = c.why ? c.why : w;
+    return -1;
+  };
+  if (!buf || n < 0) return bad("no stream");
+  uint8_t want[kSavedPrefixMax];
+  Writer hw{want};
+  emit_map_header(hw, 0, 0, 0);
+  // [header to loadFactor][threshold][77 08][buckets][size]
+  int32_t threshold, buckets, size;
+  if (!c.expect(want, hw.n - 14, "not a HashMap<Integer,double[]> stream") || !c.i32(threshold) ||
+      !c.expect(want + hw.n - 10, 2, "HashMap block data") || !c.i32(buckets) || !c.i32(size))
+    return bad("malformed stream");
+  if (buckets < 16 || (buckets & (buckets - 1)) || buckets > (1 << 30)) return bad("bucket count is not a table size");
+  if (size < 0) return bad("negative map size");
+  // a table never allocated (no put yet) has threshold 0; any other holds at most 0.75 * buckets entries
+  if (!(size == 0 && threshold == 0) && threshold != buckets / 4 * 3) return bad("threshold is not 0.75 * buckets");
+  if (size > threshold) return bad("more entries than the threshold");
+  if (size > (n - c.i) / 20 + 1) return bad("truncated stream");
+  std::vector<int32_t> seen;
+  seen.reserve((size_t)size);
+  for (int32_t e = 0; e < size; ++e) {
+    Writer ew{want};
+    emit_map_entry(ew, e == 0, 0, 0);
+    // the framing up to the key, then the framing between key and array length
+    const int64_t k1 = e == 0 ? 73 : 6, k2 = e == 0 ? 19 : 6;
+    int32_t key, len;
+    if (!c.expect(want, k1, "entry key is not an Integer") || !c.i32(key) ||
+        !c.expect(want + k1 + 4, k2, "entry value is not a double[]") || !c.i32(len))
+      return bad("malformed stream");
+    if (len < 0) return bad("negative array length");
+    if (int64_t(len) * 8 > n - c.i) return bad("array overruns the stream");
+    seen.push_back(key);
+    if (e < max_entries) {
+      if (keys) keys[e] = key;
+      if (lens) lens[e] = len;
+      if (offs) offs[e] = c.i;
+    }
+    c.i += int64_t(len) * 8;
+  }
+  const uint8_t end = TC_ENDBLOCKDATA;
+  if (!c.expect(&end, 1, "map without its end marker")) return bad("malformed stream");
+  if (c.i != n) return bad("bytes after the map");
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return bad("duplicate key");
+  return size;
+}
+
+int64_t parse_darr(const uint8_t* buf, int64_t n, int64_t* payload_off, const char** why) {
+  Cursor c{buf, n};
+  auto bad = [&](const char* w) -> int64_t {
+    if (why) *why = c.why ? c.why : w;
+    return -1;
+  };
+  if (!buf || n < 0) return bad("no stream");
+  uint8_t want[32];
+  Writer w{want};
+  emit_darr_header(w, 0);
+  int32_t len;
+  if (!c.expect(want, w.n - 4, "not a double[] stream") || !c.i32(len)) return bad("malformed stream");
+  if (len < 0) return bad("negative array length");
+  if (int64_t(len) * 8 > n - c.i) return bad("array overruns the stream");
+  if (c.i + int64_t(len) * 8 != n) return bad("bytes after the array");
+  if (payload_off) *payload_off = c.i;
+  return len;
+}
+
+int64_t parse_dlist(const uint8_t* buf, int64_t n, const char** why) {
+  Cursor c{buf, n};
+  auto bad = [&](const char* w) -> int64_t {
+    if (why) *why = c.why ? c.why : w;
+    return -1;
+  };
+  if (!buf || n < 0) return bad("no stream");
+  uint8_t want[kSavedPrefixMax];
+  Writer w{want};
+  emit_dlist_header(w, 1);
+  int32_t size, cap;
+  // [header to the size field][size][77 04][size][first Double's descriptors]
+  if (!c.expect(want, 47, "not an ArrayList<Double> stream") || !c.i32(size) ||
+      !c.expect(want + 51, 2, "ArrayList block data") || !c.i32(cap))
+    return bad("malformed stream");
+  if (size < 0) return bad("negative list size");
+  if (cap != size) return bad("list capacity differs from its size");
+  if (dlist_total(size) != n) return bad("stream length does not match the list size");
+  if (size > 0 && !c.expect(want + 57, kDlistFirst - 57, "first element is not a Double")) return bad("malformed stream");
+  if (buf[n - 1] != TC_ENDBLOCKDATA) return bad("list without its end marker");
+  return size;
 }
 
 }  // namespace javaser

@@ -277,6 +277,43 @@ class IPLS {
     return out;
   }
 
+  // save_model (IPLS.java:1904-1911, called by terminate, :1981-1998): the
+  // file bytes of the HashMap<Integer,double[]> of Weights[p] for p in
+  // Auth_List (ObjectOutputStream), packed on the device.
+  std::vector<uint8_t> save_model() {
+    return sized([&](uint8_t* out, int64_t cap) {
+      return ipls_agg_save_model(h_.get(), Auth_List.data(), (int)Auth_List.size(), IPLS_TGT_WEIGHTS, out, cap);
+    });
+  }
+  // _Upload_File(Weights[Partition], ...) (IPLS.java:136-140): one partition as a serialised double[].
+  std::vector<uint8_t> save_partition(int Partition) {
+    return sized([&](uint8_t* out, int64_t cap) {
+      return ipls_agg_save_partition(h_.get(), Partition, IPLS_TGT_WEIGHTS, out, cap);
+    });
+  }
+  // The pid-5 reply `<ID>Model` and init's `<ID>ETHModel` (IPLS.java:547-558,
+  // 2255-2273): every Weights[i][j] in order as a serialised ArrayList<Double>.
+  std::vector<uint8_t> Model_list() {
+    return sized([&](uint8_t* out, int64_t cap) { return ipls_agg_save_model_list(h_.get(), IPLS_TGT_WEIGHTS, out, cap); });
+  }
+  // DownloadParameters(hash) -> InitializeWeights (IPLS.java:567): the same list's bytes.
+  void InitializeWeights_from_list(const std::vector<uint8_t>& list_file) {
+    check(ipls_agg_load_model(h_.get(), list_file.data(), (int64_t)list_file.size(), IPLS_HOST_DLIST), h_.get());
+  }
+  // DownloadMapParameters(fileHash) and the LeavingPeer requests it queues for
+  // every partition of ChangedList (IPLS.java:728-731), which the Updater
+  // blends in: W[p] = a*W[p] + (1-a)*parameters.get(p), a = 0.6
+  // (Updater.java:65-69).  One call; returns the partitions blended.
+  int DownloadMapParameters(const std::vector<uint8_t>& map_file, const std::vector<int32_t>& ChangedList) {
+    const double a = 0.6;   // Updater.java:17
+    int32_t applied = 0;
+    if (ChangedList.empty()) return 0;   // (a null list would mean every key of the file)
+    check(ipls_agg_load_saved(h_.get(), map_file.data(), (int64_t)map_file.size(), IPLS_SAVED_BLEND, IPLS_TGT_WEIGHTS,
+                              ChangedList.data(), (int)ChangedList.size(), a, 1 - a, &applied),
+          h_.get());
+    return applied;
+  }
+
   // Wait_Client_Gradients' publish loop (IPLS.java:1423-1431, direct
   // communication): for every partition i of Auth_List, ipfsClass.send(topic,
   // Marshall_Packet(Aggregated_Gradients[i], id, middleware_iteration,
@@ -339,6 +376,16 @@ class IPLS {
   struct Closer {
     void operator()(ipls_agg* h) const { ipls_agg_close(h); }
   };
+  // a size-then-fill entry point: fn(out, cap) with out == nullptr returns the byte count
+  template <class F>
+  std::vector<uint8_t> sized(F fn) {
+    const int64_t n = fn(nullptr, 0);
+    if (n < 0) raise((int)n, h_.get());
+    std::vector<uint8_t> out((size_t)n);
+    const int64_t m = fn(out.data(), n);
+    if (m < 0) raise((int)m, h_.get());
+    return out;
+  }
   PeerData cfg_;
   std::unique_ptr<ipls_agg, Closer> h_;
 
@@ -381,6 +428,14 @@ class Updater {
   void _Update_from_partial(const std::vector<uint8_t>& pair_file, int Partiton) {
     check(ipls_agg_accumulate(ipls_.handle(), Partiton, IPLS_TGT_REP, pair_file.data(), (int64_t)pair_file.size(),
                               IPLS_HOST_PAIR),
+          ipls_.handle());
+  }
+  // The "LeavingPeer" branch (Updater.java:65-69) for one partition handed
+  // over as a serialised double[] (IPLS.java:136-140).
+  void _Update_from_leaving_peer(const std::vector<uint8_t>& array_file, int Partiton) {
+    const double a = 0.6;   // Updater.java:17
+    check(ipls_agg_blend(ipls_.handle(), Partiton, IPLS_TGT_WEIGHTS, array_file.data(), (int64_t)array_file.size(),
+                         IPLS_HOST_DARR, a, 1 - a),
           ipls_.handle());
   }
   // ThreadReceiver pid 3 -> queue -> _Update (IPLS.java:453-465): a decoded frame.

@@ -6,14 +6,16 @@ The arithmetic runs in hand-written gfx950 HIP kernels inside
 binding plus the Middleware wire codec.
 """
 from ._native import (  # noqa: F401
-    ALL_PARTITIONS, DEV_BE, DEV_F64, DEV_TEXT, HOST_BE, HOST_BE_CANON, HOST_F64, HOST_FRAME, HOST_PAIR,
+    ALL_PARTITIONS, DEV_BE, DEV_F64, DEV_TEXT, HOST_BE, HOST_BE_CANON, HOST_DARR, HOST_DLIST, HOST_F64, HOST_FRAME,
+    HOST_PAIR,
     HOST_TEXT, KERNEL_FOLD1, KERNEL_REDUCE, KERNEL_REDUCE_SCALAR, KERNEL_ROUND, SHAPE_BIG, SHAPE_HALF, SHAPE_MID,
     SHAPE_SMALL, START_ACCUM, START_FIRST, START_ZERO, TGT_AGG, TGT_FUTURE, TGT_REP, TGT_WADDR, TGT_WEIGHTS,
-    IplsError, build_info, lib,
+    SAVED_BLEND, SAVED_SET, IplsError, build_info, lib,
 )
 from .aggregator import (  # noqa: F401
-    Aggregator, DeviceBuffer, PinnedBuffer, checksum_dev, encode_secure, frame_encode, frame_parse, java_pair_hash,
-    pair_encode, pair_parse, shard_plan, synth_fill,
+    Aggregator, DeviceBuffer, PinnedBuffer, checksum_dev, encode_darr, encode_dlist, encode_saved, encode_secure,
+    frame_encode, frame_parse, java_pair_hash, pair_encode, pair_parse, parse_darr, parse_dlist, parse_saved,
+    shard_plan, synth_fill,
 )
 
 SEED = 0x1B5_2026  # synthetic workload seed (SURVEY.md §8(d))

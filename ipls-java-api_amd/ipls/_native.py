@@ -23,6 +23,8 @@ IPLS_E_DEVICE, IPLS_E_FORMAT, IPLS_E_NODEV = -5, -6, -7
 TGT_AGG, TGT_REP, TGT_WEIGHTS, TGT_WADDR, TGT_FUTURE = 0, 1, 2, 3, 4
 HOST_F64, HOST_BE, HOST_FRAME, DEV_F64, DEV_BE, HOST_BE_CANON, HOST_PAIR = 0, 1, 2, 3, 4, 5, 6
 HOST_TEXT, DEV_TEXT = 7, 8
+HOST_DARR, HOST_DLIST = 9, 10
+SAVED_SET, SAVED_BLEND = 0, 1
 KERNEL_REDUCE, KERNEL_ROUND, KERNEL_FOLD1, KERNEL_REDUCE_SCALAR = 1, 2, 3, 4
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
@@ -34,6 +36,9 @@ CHUNK_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctyp
                               ctypes.c_int64)
 # ipls_chunk_source: int (*)(void *ctx, void *dst, int64_t offset, int64_t n)
 CHUNK_SOURCE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64)
+# ipls_byte_sink: int (*)(void *ctx, const uint8_t *bytes, int64_t offset, int64_t n)
+BYTE_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64,
+                             ctypes.c_int64)
 
 ERROR_NAMES = {
     IPLS_E_INVAL: "IllegalArgument",
@@ -148,6 +153,18 @@ SIGNATURES = {
     "ipls_agg_publish_partial": (_i64, [_vp, _i, _i, _i32, _i32, _i16, _vp, _i32, _vp, _i64, _i]),
     "ipls_agg_publish_partials": (_i64, [_vp, _vp, _i, _i, _i32, _vp, _i16, _vp, _i32, _vp, _i64, _i, _vp, _vp]),
     "ipls_agg_last_launch": (_i, [_vp, _P(LaunchInfo)]),
+    # saved-model files; the host-only encoders take typed first pointers (NULL is a valid empty input)
+    "ipls_saved_parse": (_i64, [_vp, _i64, _P(_i32), _P(_i64), _P(_i64), _i64]),
+    "ipls_saved_encode": (_i64, [_P(_i32), _i, _P(_vp), _P(_i64), _i, _vp, _i64]),
+    "ipls_darr_parse": (_i64, [_vp, _i64, _P(_i64)]),
+    "ipls_darr_encode": (_i64, [_P(ctypes.c_uint8), _i64, _i, _vp, _i64]),
+    "ipls_dlist_parse": (_i64, [_vp, _i64, _P(ctypes.c_double), _i64]),
+    "ipls_dlist_encode": (_i64, [_P(ctypes.c_uint8), _i64, _i, _vp, _i64]),
+    "ipls_agg_save_model": (_i64, [_vp, _P(_i32), _i, _i, _vp, _i64]),
+    "ipls_agg_save_model_chunked": (_i, [_vp, _P(_i32), _i, _i, _i64, _vp, _vp]),   # sink: a BYTE_SINK instance
+    "ipls_agg_save_partition": (_i64, [_vp, _i, _i, _vp, _i64]),
+    "ipls_agg_save_model_list": (_i64, [_vp, _i, _vp, _i64]),
+    "ipls_agg_load_saved": (_i, [_vp, _vp, _i64, _i, _i, _P(_i32), _i, ctypes.c_double, ctypes.c_double, _P(_i32)]),
 }
 
 _lib = None

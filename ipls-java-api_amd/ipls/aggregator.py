@@ -213,9 +213,15 @@ class Aggregator:
         return v.value
 
     # ---- reference operations ----
-    def InitializeWeights(self, model, big_endian: bool = False):
-        """IPLS.java:1880-1901 (model = List<Double>, or read_file's raw BE bytes)."""
-        ptr, n, kind, keep = _operand(model, big_endian)
+    def InitializeWeights(self, model, big_endian: bool = False, *, java_list: bool = False):
+        """IPLS.java:1880-1901 (model = List<Double>, or read_file's raw BE
+        bytes; ``java_list=True``: the bytes of a Java-serialised
+        ArrayList<Double>, what DownloadParameters reads, IPLS.java:567)."""
+        if java_list:
+            keep = _u8(model)
+            ptr, n, kind = keep.ctypes.data, keep.size, N.HOST_DLIST
+        else:
+            ptr, n, kind, keep = _operand(model, big_endian)
         self._chk(self._lib.ipls_agg_load_model(self._h, ptr, n, kind))
 
     def OrganizeGradients(self, gradients, big_endian_out: bool = False) -> dict[int, np.ndarray]:
@@ -566,6 +572,64 @@ class Aggregator:
         self._chk(self._lib.ipls_agg_commit_partial(self._h, partition, workers, out.ctypes.data, n))
         return out.tobytes()
 
+    # ---- saved-model files (IPLS.save_model / DownloadMapParameters) ----
+    def _two_calls(self, fn, *args) -> bytes:
+        """A size-then-fill entry point: fn(handle, *args, out, out_cap)."""
+        n = self._chk(fn(self._h, *args, None, 0))
+        out = np.empty(n, dtype=np.uint8)
+        self._chk(fn(self._h, *args, out.ctypes.data, n))
+        return out.tobytes()
+
+    def save_model(self, auth_list=None, *, sink=None, target: int = N.TGT_WEIGHTS, chunk_bytes: int = 4 << 20):
+        """IPLS.save_model (IPLS.java:1904-1911): the Java-serialised
+        HashMap<Integer,double[]> of Weights[p] for p in ``auth_list`` (default:
+        every partition), packed on the device.  Returns the file's bytes, or
+        with ``sink(ptr, offset, count)`` hands them over piece by piece
+        (ipls_agg_save_model_chunked; the sink returns True to go on)."""
+        parts = list(range(self.n_partitions)) if auth_list is None else [int(p) for p in auth_list]
+        cp = (ctypes.c_int32 * max(len(parts), 1))(*parts)
+        if sink is None:
+            return self._two_calls(self._lib.ipls_agg_save_model, cp, len(parts), target)
+        caught = []
+
+        @N.BYTE_SINK
+        def cb(ctx, b, off, cnt):
+            return _callback(caught, sink, ctypes.cast(b, ctypes.c_void_p).value, off, cnt)
+        rc = self._lib.ipls_agg_save_model_chunked(self._h, cp, len(parts), target, chunk_bytes, cb, None)
+        _reraise(caught)
+        self._chk(rc)
+        return None
+
+    def save_partition(self, partition: int, *, target: int = N.TGT_WEIGHTS) -> bytes:
+        """The serialised double[] of one partition: the single-partition
+        hand-over file (MyIPFSClass.java:261-270, IPLS.java:136-140)."""
+        return self._two_calls(self._lib.ipls_agg_save_partition, partition, target)
+
+    def save_model_list(self, *, target: int = N.TGT_WEIGHTS) -> bytes:
+        """The serialised ArrayList<Double> of every partition's values in
+        order: the pid-5 `<ID>Model` reply and init's `<ID>ETHModel`
+        (IPLS.java:547-558, 2255-2273)."""
+        return self._two_calls(self._lib.ipls_agg_save_model_list, target)
+
+    def LoadSavedModel(self, file_bytes, parts=None, *, leaving_peer: bool = False,
+                       target: int = N.TGT_WEIGHTS) -> int:
+        """DownloadMapParameters (MyIPFSClass.java:559-566) and what follows it:
+        Weights[p] = file[p] for p in ``parts`` (the ChangedList; default every
+        key of the file), or with ``leaving_peer=True`` the Updater's blend
+        W = a*W + (1-a)*file[p], a = 0.6 (IPLS.java:728-731, Updater.java:65-69).
+        Returns the number of partitions written."""
+        a = _u8(file_bytes)
+        cp, n = None, 0
+        if parts is not None:
+            parts = [int(p) for p in parts]
+            cp, n = (ctypes.c_int32 * max(len(parts), 1))(*parts), len(parts)
+        done = ctypes.c_int32()
+        la = self.LEAVING_A
+        self._chk(self._lib.ipls_agg_load_saved(self._h, a.ctypes.data, a.size,
+                                                N.SAVED_BLEND if leaving_peer else N.SAVED_SET, target, cp, n,
+                                                la, 1 - la, ctypes.byref(done)))
+        return done.value
+
     def merge_files(self, files, *, partial_updates: bool = False) -> bytes:
         """Storage node merge (Decentralized_Storage_Receiver.java:239-258) of
         downloaded files -- raw BE gradient files (status 0) or Pair partial
@@ -908,6 +972,81 @@ def pair_encode(workers: int, gradients) -> bytes:
     n = N.check(N.lib().ipls_pair_encode(workers, g.ctypes.data, g.size, N.HOST_F64, None, 0))
     out = np.empty(n, dtype=np.uint8)
     N.check(N.lib().ipls_pair_encode(workers, g.ctypes.data, g.size, N.HOST_F64, out.ctypes.data, n))
+    return out.tobytes()
+
+
+def _u8(data) -> np.ndarray:
+    return np.frombuffer(bytes(data), dtype=np.uint8)
+
+
+def _u8_ptr(a: np.ndarray):
+    return ctypes.cast(a.ctypes.data, ctypes.POINTER(ctypes.c_uint8)) if a.size else None
+
+
+def parse_saved(data) -> dict[int, np.ndarray]:
+    """DownloadMapParameters (MyIPFSClass.java:559-566) through the C-ABI: the
+    HashMap<Integer,double[]> of a save_model file as {key: float64 array}, in
+    the file's (HashMap iteration) order."""
+    a = _u8(data)
+    n = N.check(N.lib().ipls_saved_parse(a.ctypes.data, a.size, None, None, None, 0))
+    keys = (ctypes.c_int32 * max(n, 1))()
+    lens, offs = (ctypes.c_int64 * max(n, 1))(), (ctypes.c_int64 * max(n, 1))()
+    N.check(N.lib().ipls_saved_parse(a.ctypes.data, a.size, keys, lens, offs, n))
+    return {int(keys[i]): np.frombuffer(a[offs[i]:offs[i] + 8 * lens[i]].tobytes(), dtype=">f8").astype(np.float64)
+            for i in range(n)}
+
+
+def encode_saved(weights, order=None) -> bytes:
+    """The bytes ObjectOutputStream writes for IPLS.save_model's map
+    (IPLS.java:1904-1911): `weights` maps partition -> array, put in `order`
+    (Auth_List; default: the mapping's own order)."""
+    parts = [int(p) for p in (weights.keys() if order is None else order)]
+    arrs = [np.ascontiguousarray(weights[p], dtype=np.float64) for p in parts]
+    n = len(parts)
+    cp = (ctypes.c_int32 * max(n, 1))(*parts)
+    ca = (ctypes.c_void_p * max(n, 1))(*[x.ctypes.data for x in arrs])
+    cl = (ctypes.c_int64 * max(n, 1))(*[x.size for x in arrs])
+    need = N.check(N.lib().ipls_saved_encode(cp, n, ca, cl, N.HOST_F64, None, 0))
+    out = np.empty(need, dtype=np.uint8)
+    N.check(N.lib().ipls_saved_encode(cp, n, ca, cl, N.HOST_F64, out.ctypes.data, need))
+    return out.tobytes()
+
+
+def parse_darr(data) -> np.ndarray:
+    """A serialised double[] (MyIPFSClass._Upload_File(double[], ...), :261-270)."""
+    a = _u8(data)
+    off = ctypes.c_int64()
+    n = N.check(N.lib().ipls_darr_parse(a.ctypes.data, a.size, ctypes.byref(off)))
+    return np.frombuffer(a[off.value:off.value + 8 * n].tobytes(), dtype=">f8").astype(np.float64)
+
+
+def encode_darr(values) -> bytes:
+    g = np.ascontiguousarray(values, dtype=np.float64)
+    gp = _u8_ptr(g.view(np.uint8))
+    n = N.check(N.lib().ipls_darr_encode(gp, g.size, N.HOST_F64, None, 0))
+    out = np.empty(n, dtype=np.uint8)
+    N.check(N.lib().ipls_darr_encode(gp, g.size, N.HOST_F64, out.ctypes.data, n))
+    return out.tobytes()
+
+
+def parse_dlist(data) -> np.ndarray:
+    """DownloadParameters (MyIPFSClass.java:376-385): the values of a
+    serialised ArrayList<Double>."""
+    a = _u8(data)
+    n = N.check(N.lib().ipls_dlist_parse(a.ctypes.data, a.size, None, 0))
+    out = np.empty(n, dtype=np.float64)
+    N.check(N.lib().ipls_dlist_parse(a.ctypes.data, a.size, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n))
+    return out
+
+
+def encode_dlist(values) -> bytes:
+    """ObjectOutputStream.writeObject of an ArrayList<Double> (the `<ID>Model`
+    and `<ID>ETHModel` files, IPLS.java:547-558, 2255-2273)."""
+    g = np.ascontiguousarray(values, dtype=np.float64)
+    gp = _u8_ptr(g.view(np.uint8))
+    n = N.check(N.lib().ipls_dlist_encode(gp, g.size, N.HOST_F64, None, 0))
+    out = np.empty(n, dtype=np.uint8)
+    N.check(N.lib().ipls_dlist_encode(gp, g.size, N.HOST_F64, out.ctypes.data, n))
     return out.tobytes()
 
 

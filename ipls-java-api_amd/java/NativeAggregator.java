@@ -164,6 +164,17 @@ public final class NativeAggregator implements AutoCloseable {
         return out;
     }
 
+    /** IPLS.save_model (IPLS.java:1904-1911): the file bytes of the HashMap&lt;Integer,double[]&gt; of
+     *  Weights[p] for p in Auth_List, packed on the device (upload them with ipfs add). */
+    public byte[] saveModel(int[] authList) { return saveModel(handle, authList); }
+
+    /** DownloadMapParameters + the Updater's LeavingPeer branch (IPLS.java:728-731, Updater.java:65-69):
+     *  W[p] = 0.6 * W[p] + (1 - 0.6) * file[p] for p in changedList (null: every key); with
+     *  leavingPeer false W[p] = file[p].  Returns the number of partitions written. */
+    public int loadSavedModel(byte[] catBytes, int[] changedList, boolean leavingPeer) {
+        return loadSavedModel(handle, catBytes, changedList, leavingPeer);
+    }
+
     /** Download_Scheduler.java:324: a replica's Pair partial update, folded into REP. */
     public void updateFromPartial(byte[] catBytes, int p) { accumulatePair(handle, p, TGT_REP, catBytes); }
 
@@ -326,6 +337,8 @@ public final class NativeAggregator implements AutoCloseable {
     private static native long commitPartialLen(long h, int p, int workers);
     private static native void commitPartial(long h, int p, int workers, byte[] out);
     private static native void accumulatePair(long h, int p, int target, byte[] file);
+    private static native byte[] saveModel(long h, int[] parts);
+    private static native int loadSavedModel(long h, byte[] file, int[] parts, boolean leavingPeer);
     private static native byte[] mergeFiles(long h, byte[][] files, boolean partialUpdates);
     private static native void otherReplicaDirect(long h, int p, int aggregator, int keyHash, ByteBuffer buf, int pos,
                                                   long n);

@@ -798,6 +798,73 @@ JNIEXPORT void JNICALL Java_NativeAggregator_accumulatePair(JNIEnv *env, jclass 
     CHECK(LIB(ipls_agg_accumulate(H(h), p, tgt, src, n, IPLS_HOST_PAIR)), H(h));
 }
 
+/* The byte sink of saveModel: file bytes [off, off + n) straight from the
+ * library's pinned ring into the byte[] (sized by ipls_agg_save_model first). */
+struct file_sink { JNIEnv *env; jbyteArray out; };
+static int file_sink_fn(void *ctx, const uint8_t *bytes, int64_t off, int64_t n) {
+    struct file_sink *f = (struct file_sink *)ctx;
+    (*f->env)->SetByteArrayRegion(f->env, f->out, (jsize)off, (jsize)n, (const jbyte *)bytes);
+    return (*f->env)->ExceptionCheck(f->env) ? 1 : 0;
+}
+
+/* IPLS.save_model (IPLS.java:1904-1911): the serialised HashMap<Integer,double[]>
+ * of Weights[p] for p in parts (Auth_List), as one call: the payloads are packed
+ * on the device into a snapshot of this call, then copied piece by piece. */
+JNIEXPORT jbyteArray JNICALL Java_NativeAggregator_saveModel(JNIEnv *env, jclass c, jlong h, jintArray parts) {
+    (void)c;
+    jbyteArray res = NULL;
+    const jsize n = parts ? (*env)->GetArrayLength(env, parts) : 0;
+    jint *pp = NULL;
+    if (n > 0) {
+        pp = (*env)->GetIntArrayElements(env, parts, NULL);
+        if (!pp) return NULL;   /* OutOfMemoryError pending */
+    }
+    const int64_t total = LIB(ipls_agg_save_model(H(h), (const int32_t *)pp, n, IPLS_TGT_WEIGHTS, NULL, 0));
+    if (total < 0) {
+        throw_for(env, (int)total, H(h));
+    } else if (total > INT32_MAX) {
+        throw_msg(env, "java/lang/OutOfMemoryError", "saved model longer than a byte[]");
+    } else if ((res = (*env)->NewByteArray(env, (jsize)total)) != NULL) {
+        struct file_sink fs = {env, res};
+        const int rc = LIB(ipls_agg_save_model_chunked(H(h), (const int32_t *)pp, n, IPLS_TGT_WEIGHTS, (int64_t)8 * RING_CHUNK,
+                                                       file_sink_fn, &fs));
+        if (rc < 0) {
+            if (!(*env)->ExceptionCheck(env)) throw_for(env, rc, H(h));
+            res = NULL;
+        }
+    }
+    if (pp) (*env)->ReleaseIntArrayElements(env, parts, pp, JNI_ABORT);
+    return res;
+}
+
+/* DownloadMapParameters (MyIPFSClass.java:559-566) and the Updater's use of
+ * the map (IPLS.java:728-731, Updater.java:65-69): Weights[p] = file[p], or
+ * the leaving-peer blend 0.6 * W + (1 - 0.6) * file[p], for p in parts (null:
+ * every key of the file).  Returns the number of partitions written. */
+JNIEXPORT jint JNICALL Java_NativeAggregator_loadSavedModel(JNIEnv *env, jclass c, jlong h, jbyteArray file,
+                                                              jintArray parts, jboolean leaving) {
+    (void)c;
+    if (!file) { throw_iae(env, "null file"); return -1; }
+    const jsize n = (*env)->GetArrayLength(env, file);
+    void *src = copy_bytes(env, file, n, 0);
+    if (!src) return -1;
+    const jsize np = parts ? (*env)->GetArrayLength(env, parts) : 0;
+    jint *pp = NULL;
+    static const int32_t none = 0;   /* an empty ChangedList is not "every key" */
+    if (np > 0) {
+        pp = (*env)->GetIntArrayElements(env, parts, NULL);
+        if (!pp) return -1;   /* OutOfMemoryError pending */
+    }
+    int32_t done = 0;
+    const double a = 0.6;            /* Updater.java:17 */
+    const int rc = LIB(ipls_agg_load_saved(H(h), (const uint8_t *)src, n, leaving ? IPLS_SAVED_BLEND : IPLS_SAVED_SET,
+                                           IPLS_TGT_WEIGHTS, parts ? (pp ? (const int32_t *)pp : &none) : NULL, np, a, 1 - a,
+                                           &done));
+    if (pp) (*env)->ReleaseIntArrayElements(env, parts, pp, JNI_ABORT);
+    CHECK(rc, H(h));
+    return rc < 0 ? -1 : done;
+}
+
 JNIEXPORT jbyteArray JNICALL Java_NativeAggregator_mergeFiles(JNIEnv *env, jclass c, jlong h, jobjectArray files,
                                                                 jboolean partial) {
     (void)c;
