@@ -105,6 +105,28 @@ extern "C" {
                                 `<ID>ETHModel`, IPLS.java:547-558, 2255-2273; read by
                                 DownloadParameters, MyIPFSClass.java:376-385); n = byte
                                 length; ipls_agg_load_model only                            */
+/* The float32 trainer boundary.  The reference's trainer hands IPLS widened floats
+ * (Model.java:423: Doubles.asList(gradient.getRow(0).toDoubleVector()) of a float INDArray)
+ * and narrows what it takes back (Model.java:388-390: Dumm.put(0, j, arr.get(j)) before
+ * model.setParams).  With these kinds the library does both on the device: a source is
+ * read as floats, v = (double)src[i] (exact: signs, subnormals and NaNs as Java's
+ * widening), then exactly what the F64 kind does -- so the bits are those of the F64 call
+ * fed the widened values; an output is the F64 kind's value (the IEEE double quotient of
+ * GetPartitions, secure mode included) rounded ONCE to float, ties to even (overflow to
+ * +-inf, subnormal results kept, -0.0 kept): Java's (float)d.  n counts ELEMENTS.
+ *   sources: ipls_agg_update_gradient, ipls_agg_split (src), ipls_agg_load_model,
+ *            ipls_agg_accumulate, ipls_agg_accumulate_async (both kinds);
+ *            ipls_agg_reduce_batch, ipls_agg_reduce_batch_out, ipls_agg_aggregate_round
+ *            (bufs: DEV_F32; the destinations stay F64 / BE)
+ *   outputs: ipls_agg_get_partitions (out_kind), ipls_agg_aggregate_round (avg_kind)
+ * Every other call stays F64-only and refuses them with IPLS_E_INVAL like an unknown
+ * kind: the chunked calls, accumulate_range / read_range, the JNI natives, the BE, frame
+ * and Java-serialised formats, set_weights, blend, other_replica, reduce_partial /
+ * combine_partials, read, and the saved-model calls.  A count slot of an f32 bucket is
+ * 1.0f.  A HOST_F32 operand crosses PCIe as 4 B per element (pinned ones too: they are
+ * copied, not read zero-copy). */
+#define IPLS_DEV_F32     11  /* device float*, 4-byte aligned                                 */
+#define IPLS_HOST_F32    12  /* host float[] (native byte order)                              */
 
 /* ---- ipls_agg_load_saved modes ---- */
 #define IPLS_SAVED_SET    0  /* target[p] = file[p]                                          */
@@ -630,6 +652,9 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
 #define IPLS_KERNEL_ROUND         2  /* k_round (fused) */
 #define IPLS_KERNEL_FOLD1         3  /* k_fold1         */
 #define IPLS_KERNEL_REDUCE_SCALAR 4  /* k_reduce_scalar */
+#define IPLS_KERNEL_REDUCE_F32    5  /* k_reduce_f32: DEV_F32 buckets; a tile is block x 4 x vectors
+                                        elements; shape 0; seqf 1 when every operand was 16-B
+                                        aligned (vector path), 0 for the element-by-element form */
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2
 #define IPLS_SHAPE_SMALL  3

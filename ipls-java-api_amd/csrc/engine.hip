@@ -151,7 +151,7 @@ struct ipls_dev {
   // first (IPLS_LOCK).  Pinned host buckets fold at once (zero copy).
   struct Pending {
     std::vector<const void*> bufs;
-    bool be = false;
+    int fmt = 0;   // the queue's bucket format: 0 native doubles, 1 big-endian, 2 floats (DEV_F32)
   };
   // queue of (target, p) at pend[target * P + p]; pend_keys lists the
   // non-empty ones (a flat table: the per-arrival call is a few loads and a
@@ -833,6 +833,44 @@ void launch_reduce_scalar(bool be_in, bool be_out, int start, dim3 grid, hipStre
 #undef RS
 }
 
+// ---- kernel dispatch: k_reduce_f32 (DEV_F32 buckets) ----
+// One shape for every grid: 1024-lane workgroups, 2 vectors of 4 floats per
+// lane (32 KiB of a bucket per block, 16 accumulator VGPRs), the next peer's 2
+// loads issued before this peer's values are added (PF = 1; 70 VGPRs, no
+// spills).  Same process, same buckets, single launches
+// (tools/reduce_f32_sweep.hip, profiles/f32_boundary/sweep_*.txt): config C's
+// 16 x 4M x 32 at 79.8 % of 8 TB/s against 70.3-77.0 % for the other
+// prefetching shapes of 256..1024 lanes x 2..8 vectors and 70.6-79.8 % without
+// the prefetch; 1 x 4M x 32 at 82.4 %, the best of the sweep; ETHModel's
+// 3 x 147,870 x 3 within 5 % of the best.  Partial last tiles are scheduled
+// first (map 3) as for k_reduce.  vec: every bucket and destination is 16-B
+// aligned; otherwise the same grid runs element by element.
+constexpr int kF32BS = 1024, kF32R = 2, kF32PF = 1;
+ipls_launch_info launch_reduce_f32(bool be_out, int start, bool vec, int64_t maxL, int n_parts, hipStream_t st,
+                                   const float* const* bufs, const PartDesc* parts, int k) {
+  const int64_t tile = (int64_t)kF32BS * 4 * kF32R;
+  const int64_t tpp = (maxL + tile - 1) / tile;
+  const bool partial = tpp > 1 && maxL % tile != 0;
+  const dim3 grid((unsigned)(tpp * n_parts));
+#define RF(BO, ST, MAP, V)                                                                                        \
+  hipLaunchKernelGGL((k_reduce_f32<BO, ST, kF32R, kF32BS, MAP, V, (V ? kF32PF : 0)>), grid, dim3(kF32BS), 0, st, bufs, \
+                     parts, k, (int)tpp, n_parts)
+#define RF3(BO, ST)                                         \
+  do {                                                      \
+    if (!vec) RF(BO, ST, 0, false);                         \
+    else if (partial) RF(BO, ST, 3, true);                  \
+    else RF(BO, ST, 0, true);                               \
+  } while (0)
+#define RF2(BO) do { if (start == kZero) RF3(BO, kZero); else if (start == kFirst) RF3(BO, kFirst); else RF3(BO, kAccum); } while (0)
+  if (be_out) RF2(true);
+  else RF2(false);
+#undef RF2
+#undef RF3
+#undef RF
+  return launch_info(IPLS_KERNEL_REDUCE_F32, 0, kF32BS, kF32R, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false,
+                     be_out, start);
+}
+
 // Core of accumulate / reduce_batch: all pointers device-resident.  The
 // destination is the handle's `target` accumulators, or -- when ext_dst is
 // given -- one caller buffer per partition (doubles or, be_out, BE bytes).
@@ -848,7 +886,9 @@ struct FinOut {
 // above 256..4096 (tools/h2d_bench.hip, profiles/r01/h2d_bench_fold1.txt).
 int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, int k, bool be_in,
                int start_mode, int target, void* const* ext_dst = nullptr, bool be_out = false,
-               const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr) {
+               const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr,
+               bool f32_in = false) {
+  // f32_in: the buckets hold floats (DEV_F32), 4-B aligned; never with be_in or fin
   // lens: lengths of caller destinations that are not this engine's
   // partitions (ext_dst only, e.g. a replica slot's partial sums)
   auto len_of = [&](int q) -> int64_t { return lens ? lens[q] : h->len[p_first + q]; };
@@ -886,7 +926,7 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   }
   // one bucket into one partition (every per-arrival fold): pointers go as
   // kernel arguments, no table upload
-  if (!fin && n_parts == 1 && k == 1 && bufs[0]) {
+  if (!fin && !f32_in && n_parts == 1 && k == 1 && bufs[0]) {
     unsigned long long* d0 = dst_of(0);
     const int64_t L = len_of(0);
     if (d0 && !((uintptr_t)bufs[0] & 15) && !((uintptr_t)d0 & 15) && L > 0) {
@@ -912,7 +952,8 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   for (int64_t i = 0; i < (int64_t)n_parts * k; ++i) {
     if (!bufs[i]) return fail(h, IPLS_E_INVAL, "bucket pointer %lld is NULL", (long long)i);
     uintptr_t a = (uintptr_t)bufs[i];
-    if (a & 7) return fail(h, IPLS_E_INVAL, "bucket %lld not 8-byte aligned", (long long)i);
+    if (a & (f32_in ? 3 : 7))
+      return fail(h, IPLS_E_INVAL, "bucket %lld not %d-byte aligned", (long long)i, f32_in ? 4 : 8);
     if (a & 15) aligned16 = false;
   }
   // table = [PartDesc x n_parts][ptr x n_parts*k]
@@ -943,13 +984,16 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   const PartDesc* dparts = (const PartDesc*)dtab;
   auto dbufs = (const unsigned long long* const*)((char*)dtab + desc_bytes);
   if (fin) {
-    if (!aligned16) return fail(h, IPLS_E_INVAL, "fused round needs 16-B aligned buckets");
+    if (!aligned16 || f32_in) return fail(h, IPLS_E_INVAL, "fused round needs 16-B aligned F64/BE buckets");
     h->last_launch = launch_reduce_fin(be_in, start, h->secure, maxL, n_parts, h->stream, dbufs, dparts, k, h->d_cnt);
     HIP_TRY(h, hipGetLastError());
     for (int q = p_first; q < p_first + n_parts; ++q) h->agg_zero[q] = h->rep_zero[q] = 1;
     return IPLS_OK;
   }
-  if (aligned16) {
+  if (f32_in) {
+    h->last_launch = launch_reduce_f32(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
+                                       (const float* const*)dbufs, dparts, k);
+  } else if (aligned16) {
     h->last_launch = launch_reduce(be_in, be_out, start, maxL, n_parts, h->stream, dbufs, dparts, k);
   } else {
     const int64_t tile = (int64_t)kBlock * 8;
@@ -1273,13 +1317,14 @@ int flush_pending(ipls_dev* h) {
     size_t j = i + 1;
     int n = 1;
     while (j < keys.size() && keys[j] == key + n && keys[j] / h->P == target && h->pend[keys[j]].bufs.size() == k &&
-           h->pend[keys[j]].be == q0.be) {
+           h->pend[keys[j]].fmt == q0.fmt) {
       ++n;
       ++j;
     }
     tab.clear();
     for (size_t t = i; t < j; ++t) tab.insert(tab.end(), h->pend[keys[t]].bufs.begin(), h->pend[keys[t]].bufs.end());
-    rc = reduce_dev(h, p0, n, tab.data(), (int)k, q0.be, IPLS_START_ACCUM, target);
+    rc = reduce_dev(h, p0, n, tab.data(), (int)k, q0.fmt == 1, IPLS_START_ACCUM, target, nullptr, false, nullptr, false,
+                    nullptr, q0.fmt == 2);
     i = j;
   }
   for (int key : keys) h->pend[key].bufs.clear();   // keeps the capacity
@@ -1297,13 +1342,14 @@ int dev_reduce_batch(ipls_dev* h, int p_first, int n_parts, const void* const* b
   IPLS_LOCK(h);
   if (n_parts <= 0 || p_first < 0 || p_first + n_parts > h->P)
     return fail(h, IPLS_E_RANGE, "partitions [%d,%d) out of range [0,%d)", p_first, p_first + n_parts, h->P);
-  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE)
-    return fail(h, IPLS_E_INVAL, "reduce_batch takes device buckets (DEV_F64/DEV_BE)");
+  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && src_kind != IPLS_DEV_F32)
+    return fail(h, IPLS_E_INVAL, "reduce_batch takes device buckets (DEV_F64/DEV_BE/DEV_F32)");
   if (start_mode < IPLS_START_ACCUM || start_mode > IPLS_START_FIRST) return fail(h, IPLS_E_INVAL, "bad start mode");
   if (target_off(h, 0, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
   if (k < 0 || (k > 0 && !bufs)) return fail(h, IPLS_E_INVAL, "bad bucket list");
   HIP_TRY(h, dev_use(h->device));
-  return reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, start_mode, target);
+  return reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, start_mode, target, nullptr, false, nullptr,
+                    false, nullptr, src_kind == IPLS_DEV_F32);
 }
 
 int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, int src_kind) {
@@ -1315,7 +1361,7 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
   HIP_TRY(h, dev_use(h->device));
   const int64_t L = h->len[p];
   const void* dptr = nullptr;
-  bool be = false, staged = false;
+  bool be = false, staged = false, f32 = false;
   switch (src_kind) {
     case IPLS_DEV_F64:
     case IPLS_DEV_BE:
@@ -1342,6 +1388,20 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
       staged = true;
       break;
     }
+    case IPLS_DEV_F32:
+      // a co-located trainer's float bucket, widened in the fold (Model.java:423)
+      if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
+      if ((uintptr_t)src & 3) return fail(h, IPLS_E_INVAL, "device bucket not 4-byte aligned");
+      dptr = src;
+      f32 = true;
+      break;
+    case IPLS_HOST_F32:
+      // 4 B per element cross PCIe; the widening happens on the device
+      if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
+      if ((uintptr_t)src & 3) return fail(h, IPLS_E_INVAL, "host float bucket not 4-byte aligned");
+      if (int rc = stage_bucket(h, src, (size_t)L * 4, &dptr)) return rc;
+      staged = f32 = true;
+      break;
     case IPLS_HOST_FRAME: {
       int16_t pid;
       int32_t a, b;
@@ -1385,31 +1445,35 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
       return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
   }
   const void* bl[1] = {dptr};
-  if (int rc = reduce_dev(h, p, 1, bl, 1, be, IPLS_START_ACCUM, target)) return rc;
+  if (int rc = reduce_dev(h, p, 1, bl, 1, be, IPLS_START_ACCUM, target, nullptr, false, nullptr, false, nullptr, f32))
+    return rc;
   return staged ? release_stage(h) : IPLS_OK;
 }
 
 int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_t n, int src_kind,
                               uint64_t* ticket) {
   if (!h || !ticket) return fail(h, IPLS_E_INVAL, "null argument");
-  if (src && (src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE)) {
+  if (src && (src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE || src_kind == IPLS_DEV_F32)) {
     // device bucket: queued, folded with the partition's other queued buckets
+    // (a queue holds one format: a bucket of another one flushes first, so
+    // call order is kept across F64, BE and F32 arrivals)
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = check_part(h, p)) return rc;
     if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
     if (n < h->len[p])
       return fail(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n,
                   (long long)h->len[p]);
-    if ((uintptr_t)src & 7) return fail(h, IPLS_E_INVAL, "device bucket not 8-byte aligned");
-    const bool be = src_kind == IPLS_DEV_BE;
+    const int fmt = src_kind == IPLS_DEV_BE ? 1 : src_kind == IPLS_DEV_F32 ? 2 : 0;
+    if ((uintptr_t)src & (fmt == 2 ? 3 : 7))
+      return fail(h, IPLS_E_INVAL, "device bucket not %d-byte aligned", fmt == 2 ? 4 : 8);
     // Weights and Weight_Address are one array (IPLS.java:1141): one queue
     const int qt = target == IPLS_TGT_WADDR ? IPLS_TGT_WEIGHTS : target;
     if (h->pend.empty()) h->pend.resize((size_t)5 * h->P);   // 5 targets (include/ipls_agg.h)
     ipls_dev::Pending& q = h->pend[(size_t)qt * h->P + p];
-    if (!q.bufs.empty() && q.be != be)
+    if (!q.bufs.empty() && q.fmt != fmt)
       if (int rc = flush_pending(h)) return rc;
     if (q.bufs.empty()) h->pend_keys.push_back(qt * h->P + p);
-    q.be = be;
+    q.fmt = fmt;
     q.bufs.push_back(src);
     ++h->pending_n;
     *ticket = h->ticket_next++;
@@ -1899,6 +1963,30 @@ static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, 
   return IPLS_OK;
 }
 
+// The same divide narrowed to float (k_divide_f32): d_out holds floats.
+static int divide_range_f32(ipls_dev* h, int p0, int np, float* d_out) {
+  std::vector<DivDesc> dd(np);
+  int64_t maxn = 0;
+  for (int q = 0; q < np; ++q) {
+    const int p = p0 + q;
+    dd[q] = DivDesc{h->len[p], h->w_off[p], h->flat_off[p] - h->flat_off[p0]};
+    maxn = std::max(maxn, h->len[p] - 1);
+  }
+  if (maxn <= 0) return IPLS_OK;
+  void* dtab = nullptr;
+  if (int rc = upload_table(h, dd.data(), dd.size() * sizeof(DivDesc), &dtab)) return rc;
+  const int tpp = (int)((maxn + kDivTile32 - 1) / kDivTile32);
+  const dim3 g((unsigned)tpp * np);
+  if (h->secure)
+    hipLaunchKernelGGL((k_divide_f32<true>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena,
+                       d_out, tpp);
+  else
+    hipLaunchKernelGGL((k_divide_f32<false>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena,
+                       d_out, tpp);
+  HIP_TRY(h, hipGetLastError());
+  return IPLS_OK;
+}
+
 int dev_finalize(ipls_dev* h, int p, void* sum_out, int sum_kind, double* avg_out) {
   if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
   IPLS_LOCK(h);
@@ -2074,6 +2162,21 @@ static int flat_to_device(ipls_dev* h, const void* flat, int64_t n, int kind, co
       *d = (const unsigned long long*)h->d_scratch;
       *be = kind == IPLS_HOST_BE;
       return IPLS_OK;
+    // float vectors (update_gradient / load_model only reach here with them):
+    // *d then points at floats, 4 B per element on the device and over PCIe
+    case IPLS_DEV_F32:
+      if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "device float vector not 4-byte aligned");
+      *d = (const unsigned long long*)flat;
+      *be = false;
+      return IPLS_OK;
+    case IPLS_HOST_F32:
+      if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "host float vector not 4-byte aligned");
+      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+      if (n > 0)
+        if (int rc = stage_h2d(h, h->d_scratch, flat, (size_t)n * 4)) return rc;
+      *d = (const unsigned long long*)h->d_scratch;
+      *be = false;
+      return IPLS_OK;
     default:
       return fail(h, IPLS_E_INVAL, "bad flat kind %d", kind);
   }
@@ -2084,6 +2187,7 @@ int dev_other_replica(ipls_dev* h, int p, int32_t aggregator, const void* src, i
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
   if (n < 0 || (n > 0 && !src)) return fail(h, IPLS_E_INVAL, "bad bucket");
+  if (src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32) return fail(h, IPLS_E_INVAL, "bad flat kind %d", src_kind);
   if ((src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE) && ((uintptr_t)src & 7))
     return fail(h, IPLS_E_INVAL, "device bucket not 8-byte aligned");
   HIP_TRY(h, dev_use(h->device));
@@ -2210,14 +2314,18 @@ int dev_load_model(ipls_dev* h, const void* src, int64_t n, int src_kind) {
   HIP_TRY(h, dev_use(h->device));
   const unsigned long long* d;
   bool be;
+  const bool f32 = src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32;
   // only this engine's segment [flat_base, flat_total) of the model
-  if (int rc = flat_to_device(h, (const char*)src + 8 * h->flat_base, h->flat_total - h->flat_base, src_kind, &d,
-                              &be))
+  if (int rc = flat_to_device(h, (const char*)src + (f32 ? 4 : 8) * h->flat_base, h->flat_total - h->flat_base,
+                              src_kind, &d, &be))
     return rc;
   for (int p = 0; p < h->P; ++p) {
     const int64_t L = h->len[p];
     // IPLS.java:1883-1895: values for j < min((i+1)c, M), count slot 0.0
-    if (be)
+    if (f32)
+      hipLaunchKernelGGL(k_load_model_f32, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, (const float*)d,
+                         h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+    else if (be)
       hipLaunchKernelGGL(k_load_model<true>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, d,
                          h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
     else
@@ -2254,7 +2362,21 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
   bool be_in;
   // only the partition's own slice is needed on the device
   const int64_t lo = h->flat_off[p];
-  if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
+  const bool f32 = src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32;
+  if (f32) {
+    // floats: 4 B per element; a host slice is staged into the first L + 1
+    // doubles' worth of scratch (it needs half of that), the output after it
+    if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "float vector not 4-byte aligned");
+    if (int rc = ensure_scratch(h, (size_t)(2 * L + 2) * 8)) return rc;
+    if (src_kind == IPLS_HOST_F32) {
+      if (ncopy > 0)
+        if (int rc = stage_h2d(h, h->d_scratch, (const char*)flat + lo * 4, (size_t)ncopy * 4)) return rc;
+      d = (const unsigned long long*)h->d_scratch;
+    } else {
+      d = (const unsigned long long*)((const float*)flat + lo);
+    }
+    be_in = false;
+  } else if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
     if (int rc = ensure_scratch(h, (size_t)(2 * L + 2) * 8)) return rc;
     if (ncopy > 0)
       if (int rc = stage_h2d(h, h->d_scratch, (const char*)flat + lo * 8, (size_t)ncopy * 8)) return rc;
@@ -2273,7 +2395,7 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
     return fail(h, IPLS_E_INVAL, "bad dst_kind %d", dst_kind);
   unsigned long long* out = host_out ? (unsigned long long*)((char*)h->d_scratch + (size_t)(L + 1) * 8)
                                      : (unsigned long long*)dst;
-  if (host_out && src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE)
+  if (host_out && src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE && src_kind != IPLS_HOST_F32)
     out = (unsigned long long*)h->d_scratch;
   const bool vec = al16(d) && al16(out);
   const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
@@ -2282,8 +2404,15 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
     if (vec) hipLaunchKernelGGL((k_split<BI, BO, 0, true>), g, dim3(kBlock), 0, h->stream, d, (int64_t)0, ncopy, L, out); \
     else hipLaunchKernelGGL((k_split<BI, BO, 0, false>), g, dim3(kBlock), 0, h->stream, d, (int64_t)0, ncopy, L, out); \
   } while (0)
-  if (be_in) { if (be_out) SPL(true, true); else SPL(true, false); }
+#define SPLF(BO)                                                                                                 \
+  do {                                                                                                           \
+    if (vec) hipLaunchKernelGGL((k_split_f32<BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const float*)d, (int64_t)0, ncopy, L, out); \
+    else hipLaunchKernelGGL((k_split_f32<BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const float*)d, (int64_t)0, ncopy, L, out); \
+  } while (0)
+  if (f32) { if (be_out) SPLF(true); else SPLF(false); }
+  else if (be_in) { if (be_out) SPL(true, true); else SPL(true, false); }
   else { if (be_out) SPL(false, true); else SPL(false, false); }
+#undef SPLF
 #undef SPL
   HIP_TRY(h, hipGetLastError());
   if (host_out) return d2h(h, dst, out, (size_t)L * 8);
@@ -2309,7 +2438,20 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
   bool be;
   // only this engine's segment of the gradient vector (flat_base on)
   const int64_t seg = std::max<int64_t>(0, std::min(n, h->flat_total) - h->flat_base);
-  if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
+  const bool f32 = src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32;
+  if (src_kind == IPLS_HOST_F32) {
+    // as below, 4 B per element: only the owned partitions' floats cross PCIe
+    if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "host float vector not 4-byte aligned");
+    if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(seg, 1) * 4)) return rc;
+    const char* base = (const char*)flat + 4 * h->flat_base;
+    for (int i = 0; i < n_owned; ++i) {
+      const int64_t lo = h->flat_off[owned[i]] - h->flat_base;
+      if (nc[owned[i]] > 0)
+        if (int rc = stage_h2d(h, (char*)h->d_scratch + 4 * lo, base + 4 * lo, (size_t)nc[owned[i]] * 4)) return rc;
+    }
+    d = (const unsigned long long*)h->d_scratch;
+    be = false;
+  } else if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
     // from host memory only the owned partitions' values cross PCIe: the
     // others are split by OrganizeGradients too, but never accumulated
     // (IPLS.java:1737-1743), so their bytes are never read here
@@ -2322,7 +2464,7 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     }
     d = (const unsigned long long*)h->d_scratch;
     be = src_kind == IPLS_HOST_BE;
-  } else if (int rc = flat_to_device(h, (const char*)flat + 8 * h->flat_base, seg, src_kind, &d, &be)) {
+  } else if (int rc = flat_to_device(h, (const char*)flat + (f32 ? 4 : 8) * h->flat_base, seg, src_kind, &d, &be)) {
     return rc;
   }
   for (int i = 0; i < n_owned; ++i) {
@@ -2333,7 +2475,8 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     const int64_t lo = h->flat_off[p] - h->flat_base;
     // the segment's start decides: partitions whose flat offset is odd read
     // their values at 8 mod 16 and keep the element-per-lane shape
-    const bool vec = al16(d + lo) && al16(acc);
+    // (floats: per partition too -- flat + p*chunk floats is only 4-B aligned in general)
+    const bool vec = (f32 ? al16((const float*)d + lo) : al16(d + lo)) && al16(acc);
     const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
     // Logically-zero accumulator: MODE 2 writes +0.0 + v without reading it
     // (the bits of a fold into zeros)
@@ -2342,8 +2485,15 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     if (vec) hipLaunchKernelGGL((k_split<BI, false, M, true>), g, dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc); \
     else hipLaunchKernelGGL((k_split<BI, false, M, false>), g, dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc); \
   } while (0)
-    if (be) { if (zero) UPD(true, 2); else UPD(true, 1); }
+#define UPDF(M)                                                                                                 \
+  do {                                                                                                          \
+    if (vec) hipLaunchKernelGGL((k_split_f32<false, M, true>), g, dim3(kBlock), 0, h->stream, (const float*)d, lo, nc[p], L, acc); \
+    else hipLaunchKernelGGL((k_split_f32<false, M, false>), g, dim3(kBlock), 0, h->stream, (const float*)d, lo, nc[p], L, acc); \
+  } while (0)
+    if (f32) { if (zero) UPDF(2); else UPDF(1); }
+    else if (be) { if (zero) UPD(true, 2); else UPD(true, 1); }
     else { if (zero) UPD(false, 2); else UPD(false, 1); }
+#undef UPDF
 #undef UPD
     HIP_TRY(h, hipGetLastError());
     h->agg_zero[p] = 0;
@@ -2357,9 +2507,23 @@ int dev_get_partitions(ipls_dev* h, void* out, int64_t n, int out_kind) {
   // out holds this engine's segment: flat offsets [flat_base, flat_total)
   const int64_t M = h->flat_total - h->flat_base;
   if (n < M) return fail(h, IPLS_E_RANGE, "output of %lld < model size %lld", (long long)n, (long long)M);
-  if (out_kind != IPLS_HOST_F64 && out_kind != IPLS_HOST_BE_CANON && out_kind != IPLS_DEV_F64)
+  if (out_kind != IPLS_HOST_F64 && out_kind != IPLS_HOST_BE_CANON && out_kind != IPLS_DEV_F64 &&
+      out_kind != IPLS_DEV_F32 && out_kind != IPLS_HOST_F32)
     return fail(h, IPLS_E_INVAL, "bad out_kind %d", out_kind);
   HIP_TRY(h, dev_use(h->device));
+  if (out_kind == IPLS_DEV_F32 || out_kind == IPLS_HOST_F32) {
+    // Model.java:388-390: the model narrowed to float, on the device; a host
+    // output comes back as 4 B per value
+    if ((uintptr_t)out & 3) return fail(h, IPLS_E_INVAL, "float output not 4-byte aligned");
+    float* d_f = (float*)out;
+    if (out_kind == IPLS_HOST_F32) {
+      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(M, 1) * 4)) return rc;
+      d_f = (float*)h->d_scratch;
+    }
+    if (int rc = divide_range_f32(h, 0, h->P, d_f)) return rc;
+    if (out_kind == IPLS_DEV_F32) return IPLS_OK;
+    return d2h(h, out, d_f, (size_t)M * 4);
+  }
   unsigned long long* d_out;
   if (out_kind == IPLS_DEV_F64) {
     if ((uintptr_t)out & 7) return fail(h, IPLS_E_INVAL, "device output not 8-byte aligned");
@@ -2493,15 +2657,15 @@ int dev_reduce_batch_out(ipls_dev* h, int p_first, int n_parts, const void* cons
   IPLS_LOCK(h);
   if (n_parts <= 0 || p_first < 0 || p_first + n_parts > h->P)
     return fail(h, IPLS_E_RANGE, "partitions [%d,%d) out of range [0,%d)", p_first, p_first + n_parts, h->P);
-  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE)
-    return fail(h, IPLS_E_INVAL, "reduce_batch_out takes device buckets (DEV_F64/DEV_BE)");
+  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && src_kind != IPLS_DEV_F32)
+    return fail(h, IPLS_E_INVAL, "reduce_batch_out takes device buckets (DEV_F64/DEV_BE/DEV_F32)");
   if (dst_kind != IPLS_DEV_F64 && dst_kind != IPLS_DEV_BE)
     return fail(h, IPLS_E_INVAL, "reduce_batch_out writes device buffers (DEV_F64/DEV_BE)");
   if (start_mode < IPLS_START_ACCUM || start_mode > IPLS_START_FIRST) return fail(h, IPLS_E_INVAL, "bad start mode");
   if (!dst || k < 0 || (k > 0 && !bufs)) return fail(h, IPLS_E_INVAL, "bad bucket/destination list");
   HIP_TRY(h, dev_use(h->device));
   return reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, start_mode, IPLS_TGT_AGG, dst,
-                    dst_kind == IPLS_DEV_BE);
+                    dst_kind == IPLS_DEV_BE, nullptr, false, nullptr, src_kind == IPLS_DEV_F32);
 }
 
 int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, int k, int src_kind,
@@ -2510,16 +2674,29 @@ int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const
   IPLS_LOCK(h);
   if (n_parts <= 0 || p_first < 0 || p_first + n_parts > h->P)
     return fail(h, IPLS_E_RANGE, "partitions [%d,%d) out of range [0,%d)", p_first, p_first + n_parts, h->P);
-  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE)
-    return fail(h, IPLS_E_INVAL, "aggregate_round takes device buckets (DEV_F64/DEV_BE)");
-  if (avg_out && avg_kind != IPLS_DEV_F64 && avg_kind != IPLS_HOST_F64)
-    return fail(h, IPLS_E_INVAL, "avg_kind must be DEV_F64 or HOST_F64");
+  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && src_kind != IPLS_DEV_F32)
+    return fail(h, IPLS_E_INVAL, "aggregate_round takes device buckets (DEV_F64/DEV_BE/DEV_F32)");
+  const bool f32_in = src_kind == IPLS_DEV_F32;
+  const bool f32_avg = avg_out && (avg_kind == IPLS_DEV_F32 || avg_kind == IPLS_HOST_F32);
+  if (avg_out && !f32_avg && avg_kind != IPLS_DEV_F64 && avg_kind != IPLS_HOST_F64)
+    return fail(h, IPLS_E_INVAL, "avg_kind must be DEV_F64, HOST_F64, DEV_F32 or HOST_F32");
+  if (f32_in)
+    for (int64_t i = 0; i < (int64_t)n_parts * k; ++i)   // before anything is consumed
+      if (!bufs[i] || ((uintptr_t)bufs[i] & 3)) return fail(h, IPLS_E_INVAL, "bucket %lld NULL or not 4-byte aligned", (long long)i);
   if (k < 0 || (k > 0 && !bufs)) return fail(h, IPLS_E_INVAL, "bad bucket list");
   HIP_TRY(h, dev_use(h->device));
   const int p_last = p_first + n_parts - 1;
   const int64_t n_avg = h->flat_off[p_last] + h->len[p_last] - 1 - h->flat_off[p_first];
   unsigned long long* d_avg = nullptr;
-  if (avg_out && n_avg > 0) {
+  if (f32_avg && n_avg > 0) {
+    if ((uintptr_t)avg_out & 3) return fail(h, IPLS_E_INVAL, "float output not 4-byte aligned");
+    if (avg_kind == IPLS_DEV_F32) {
+      d_avg = (unsigned long long*)avg_out;
+    } else {
+      if (int rc = ensure_scratch(h, (size_t)n_avg * 4)) return rc;
+      d_avg = (unsigned long long*)h->d_scratch;
+    }
+  } else if (avg_out && n_avg > 0) {
     if (avg_kind == IPLS_DEV_F64) {
       if ((uintptr_t)avg_out & 7) return fail(h, IPLS_E_INVAL, "device output not 8-byte aligned");
       d_avg = (unsigned long long*)avg_out;
@@ -2530,19 +2707,28 @@ int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const
   }
   bool aligned16 = true;
   for (int64_t i = 0; i < (int64_t)n_parts * k; ++i) aligned16 = aligned16 && !((uintptr_t)bufs[i] & 15);
-  if (aligned16) {
+  if (aligned16 && !f32_in && !f32_avg) {
     FinOut fo{d_avg};
     if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, IPLS_START_ACCUM, IPLS_TGT_AGG,
                             nullptr, false, &fo))
       return rc;
   } else {
     // 8-B aligned buckets (frames at odd offsets): the same three steps unfused
-    if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, IPLS_START_ACCUM, IPLS_TGT_AGG))
+    // float buckets or float averages: the f32 fold / the f32-out divide take
+    // the place of the fused kernel's halves (bit-identical by definition)
+    if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, IPLS_START_ACCUM, IPLS_TGT_AGG,
+                            nullptr, false, nullptr, false, nullptr, f32_in))
       return rc;
     if (int rc = finalize_range(h, p_first, n_parts)) return rc;
-    if (d_avg)
-      if (int rc = divide_range(h, p_first, n_parts, d_avg, false)) return rc;
+    if (d_avg) {
+      if (f32_avg) {
+        if (int rc = divide_range_f32(h, p_first, n_parts, (float*)d_avg)) return rc;
+      } else if (int rc = divide_range(h, p_first, n_parts, d_avg, false)) {
+        return rc;
+      }
+    }
   }
+  if (d_avg && avg_kind == IPLS_HOST_F32) return d2h(h, avg_out, d_avg, (size_t)n_avg * 4);
   if (d_avg && avg_kind == IPLS_HOST_F64) return d2h(h, avg_out, d_avg, (size_t)n_avg * 8);
   return IPLS_OK;
 }

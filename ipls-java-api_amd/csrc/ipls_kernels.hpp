@@ -1499,4 +1499,331 @@ __global__ __launch_bounds__(kBlock) void k_ser_unbox(const unsigned char* __res
   }
 }
 
+// ===========================================================================
+// float32 trainer boundary (Model.java:423 widens a float INDArray to the
+// doubles it hands to UpdateGradient; Model.java:388-390 narrows GetPartitions'
+// doubles back into one).  Sources are read as floats and widened in registers
+// -- (double)f is exact, subnormals included (the kernels keep f32 denormals:
+// no flush flag anywhere) -- then every expression is the f64 kernel's, so the
+// bits are those of the f64 path fed the widened values.  Outputs are the f64
+// quotient rounded once to float (v_cvt_f32_f64, ties to even).
+// ===========================================================================
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef const IPLS_GLOBAL f4* gcf4;
+typedef IPLS_GLOBAL f4* gf4;
+typedef const IPLS_GLOBAL float* gcf32;
+
+__device__ __forceinline__ f4 ld16f(const float* p) { return __builtin_nontemporal_load((gcf4)p); }
+__device__ __forceinline__ float ld4f(const float* p) { return *(gcf32)p; }
+
+// ---------------------------------------------------------------------------
+// k_reduce_f32: the batched fixed-order fold (k_reduce) over f32 buckets.
+// Grid = n_parts * tiles_per_part blocks of BS lanes; a tile is BS * 4 * R
+// elements.  A lane owns 4 consecutive elements per vector: one 16-B
+// non-temporal load per peer per vector, four widenings, four chained f64
+// adds into 4 accumulators, two 16-B stores (native doubles, or BE_OUT bytes).
+// The peer axis is walked in order per element, as in reduce_tiles.
+//   VEC : every bucket and every destination of the launch is 16-B aligned
+//         (decided by the host); full tiles then take the vector path and the
+//         partial last tile 4*BS-element vector steps with a scalar remainder.
+//         !VEC: everything element by element (buckets at 4 mod 16 etc.).
+//   MAP : 0 partition-major, 3 partial tiles first (map_block).
+//   PF  : 1 = peer j+1's R loads are issued before peer j's values are added
+//         (two peers' loads in flight per lane, the fold order unchanged).
+// ACCUM reads the target in BE_OUT's byte order, like k_reduce.
+// ---------------------------------------------------------------------------
+template <bool BE_OUT, int START, int R, int BS, int MAP, bool VEC, int PF = 0>
+__global__ __launch_bounds__(BS) void k_reduce_f32(const float* const* __restrict__ bufs,
+                                                   const PartDesc* __restrict__ parts, int k, int tiles_per_part,
+                                                   int n_parts) {
+  constexpr int64_t kTile = (int64_t)BS * 4 * R;
+  constexpr int kPB = 8;   // peers in flight on the partial-tile paths
+  int q, t;
+  map_block(MAP, gridDim.x, tiles_per_part, n_parts, q, t);
+  if (q >= n_parts) return;
+  const int64_t L = parts[q].len;
+  const int64_t base = (int64_t)t * kTile;
+  if (base >= L) return;
+  unsigned long long* __restrict__ dst = parts[q].dst;
+  const float* const* __restrict__ pb = bufs + (size_t)q * k;
+  const int tid = threadIdx.x;
+  const int j0 = (START == kFirst) ? 1 : 0;
+
+  if (VEC && base + kTile <= L) {
+    // lane's first element of the tile; vector r is r * BS * 4 elements on
+    const int64_t o0 = base + 4 * (int64_t)tid;
+    double acc[R][4];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t o = o0 + (int64_t)r * BS * 4;
+      if constexpr (START == kZero) {
+        acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+      } else if constexpr (START == kFirst) {
+        const f4 x = ld16f(pb[0] + o);
+        acc[r][0] = (double)x.x;
+        acc[r][1] = (double)x.y;
+        acc[r][2] = (double)x.z;
+        acc[r][3] = (double)x.w;
+      } else {
+        const d2 a = decode2<BE_OUT>(ld16<false>(dst + o));
+        const d2 b = decode2<BE_OUT>(ld16<false>(dst + o + 2));
+        acc[r][0] = a.x;
+        acc[r][1] = a.y;
+        acc[r][2] = b.x;
+        acc[r][3] = b.y;
+      }
+    }
+    if constexpr (PF) {
+      f4 v[R];
+      if (j0 < k) {
+        const float* __restrict__ src = pb[j0] + o0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = ld16f(src + (int64_t)r * BS * 4);
+      }
+      for (int j = j0; j < k; ++j) {
+        f4 nx[R];
+        if (j + 1 < k) {
+          const float* __restrict__ src = pb[j + 1] + o0;
+#pragma unroll
+          for (int r = 0; r < R; ++r) nx[r] = ld16f(src + (int64_t)r * BS * 4);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          acc[r][0] = acc[r][0] + (double)v[r].x;
+          acc[r][1] = acc[r][1] + (double)v[r].y;
+          acc[r][2] = acc[r][2] + (double)v[r].z;
+          acc[r][3] = acc[r][3] + (double)v[r].w;
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = nx[r];
+      }
+    } else {
+    for (int j = j0; j < k; ++j) {
+      const float* __restrict__ src = pb[j] + o0;
+      f4 v[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) v[r] = ld16f(src + (int64_t)r * BS * 4);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        acc[r][0] = acc[r][0] + (double)v[r].x;
+        acc[r][1] = acc[r][1] + (double)v[r].y;
+        acc[r][2] = acc[r][2] + (double)v[r].z;
+        acc[r][3] = acc[r][3] + (double)v[r].w;
+      }
+    }
+    }  // !PF
+    // A lane's 4 sums are 32 B, so its own two 16-B stores would each cover
+    // half of every 128-B line the wave writes (measured: WRITE_SIZE 1.12x the
+    // algorithmic 8 L).  Instead the 8 lanes that own two adjacent lines
+    // (lanes 0-3 the first, 4-7 the second) swap their upper pair of sums
+    // with lane ^ 4: the first store instruction then writes the first line
+    // whole -- lanes 0-3 their own lower pairs, lanes 4-7 the upper pairs of
+    // lanes 0-3 -- and the second one the second line.  Values only move
+    // between lanes; every sum is unchanged.
+    const bool hi = tid & 4;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t o = o0 + (int64_t)r * BS * 4;
+      const d2 own = d2{acc[r][0], acc[r][1]};
+      const d2 got = d2{__shfl_xor(acc[r][2], 4), __shfl_xor(acc[r][3], 4)};   // elements o ^ 16 .. + 2, + 3
+      __builtin_nontemporal_store(encode2<BE_OUT>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
+      __builtin_nontemporal_store(encode2<BE_OUT>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
+    }
+    return;
+  }
+  // ------- partial last tile, or a launch with a misaligned operand -------
+  const int64_t end = base + kTile < L ? base + kTile : L;
+  int64_t sb = base;
+  if constexpr (VEC) {
+    for (; sb + 4 * BS <= end; sb += 4 * BS) {
+      const int64_t o = sb + 4 * (int64_t)tid;
+      double a0, a1, a2, a3;
+      if constexpr (START == kZero) {
+        a0 = a1 = a2 = a3 = 0.0;
+      } else if constexpr (START == kFirst) {
+        const f4 x = ld16f(pb[0] + o);
+        a0 = (double)x.x, a1 = (double)x.y, a2 = (double)x.z, a3 = (double)x.w;
+      } else {
+        const d2 a = decode2<BE_OUT>(ld16<false>(dst + o));
+        const d2 b = decode2<BE_OUT>(ld16<false>(dst + o + 2));
+        a0 = a.x, a1 = a.y, a2 = b.x, a3 = b.y;
+      }
+      int jj = j0;
+      for (; jj + kPB <= k; jj += kPB) {
+        f4 v[kPB];
+#pragma unroll
+        for (int g = 0; g < kPB; ++g) v[g] = ld16f(pb[jj + g] + o);
+#pragma unroll
+        for (int g = 0; g < kPB; ++g) {
+          a0 = a0 + (double)v[g].x;
+          a1 = a1 + (double)v[g].y;
+          a2 = a2 + (double)v[g].z;
+          a3 = a3 + (double)v[g].w;
+        }
+      }
+      for (; jj < k; ++jj) {
+        const f4 x = ld16f(pb[jj] + o);
+        a0 = a0 + (double)x.x;
+        a1 = a1 + (double)x.y;
+        a2 = a2 + (double)x.z;
+        a3 = a3 + (double)x.w;
+      }
+      __builtin_nontemporal_store(encode2<BE_OUT>(d2{a0, a1}), (gu2)(dst + o));
+      __builtin_nontemporal_store(encode2<BE_OUT>(d2{a2, a3}), (gu2)(dst + o + 2));
+    }
+  }
+  for (int64_t e = sb + tid; e < end; e += BS) {
+    double acc;
+    if constexpr (START == kZero) acc = 0.0;
+    else if constexpr (START == kFirst) acc = (double)ld4f(pb[0] + e);
+    else acc = decode1<BE_OUT>(ld8(dst + e));
+    int jj = j0;
+    for (; jj + kPB <= k; jj += kPB) {
+      float v[kPB];
+#pragma unroll
+      for (int g = 0; g < kPB; ++g) v[g] = ld4f(pb[jj + g] + e);
+#pragma unroll
+      for (int g = 0; g < kPB; ++g) acc = acc + (double)v[g];
+    }
+    for (; jj < k; ++jj) acc = acc + (double)ld4f(pb[jj] + e);
+    st8(dst + e, BE_OUT ? f64_to_be(acc) : __builtin_bit_cast(unsigned long long, acc));
+  }
+}
+
+// Shape of the f32-source elementwise kernels when the partition's slice of
+// the flat vector and its destination are both 16-B aligned (VEC, decided by
+// the host per partition: flat + p*chunk is only 4-B aligned in general): a
+// block owns kEwTile consecutive elements, a lane kEwV32 vectors of 4 floats.
+constexpr int kEwV32 = 2;
+static_assert((int64_t)kBlock * 4 * kEwV32 == kEwTile, "one elementwise tile size");
+
+// k_split over a float flat vector: OrganizeGradients (MODE 0) and
+// UpdateGradient's own accumulate (MODE 1, 2), the expressions of k_split on
+// v = (double)flat[lo + i].  The tile that holds the count slot (1.0, what a
+// widened 1.0f count slot is) goes element by element.
+template <bool BE_OUT, int MODE, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_split_f32(const float* __restrict__ flat, int64_t lo, int64_t ncopy,
+                                                      int64_t L, unsigned long long* __restrict__ dst) {
+  static_assert(MODE == 0 || !BE_OUT, "the folds write native doubles");
+  auto one = [&](int64_t i) {
+    double v;
+    if (i < ncopy) v = (double)ld4f(flat + lo + i);
+    else if (i == ncopy) v = 1.0;
+    else v = 0.0;
+    if constexpr (MODE == 1) {
+      const double a = __builtin_bit_cast(double, dst[i]);
+      dst[i] = __builtin_bit_cast(unsigned long long, a + v);
+    } else if constexpr (MODE == 2) {
+      dst[i] = __builtin_bit_cast(unsigned long long, 0.0 + v);
+    } else {
+      dst[i] = BE_OUT ? f64_to_be(v) : __builtin_bit_cast(unsigned long long, v);
+    }
+  };
+  if constexpr (VEC) {
+    const int64_t base = (int64_t)blockIdx.x * kEwTile;
+    if (base + kEwTile <= ncopy) {
+      const float* src = flat + lo;
+      f4 sv[kEwV32];
+      u2 dv[kEwV32][2];
+#pragma unroll
+      for (int k = 0; k < kEwV32; ++k) {
+        const int64_t i = base + 4 * ((int64_t)k * kBlock + threadIdx.x);
+        sv[k] = ld16f(src + i);
+        if constexpr (MODE == 1) {
+          dv[k][0] = *(gcu2)(dst + i);
+          dv[k][1] = *(gcu2)(dst + i + 2);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kEwV32; ++k) {
+        const int64_t i = base + 4 * ((int64_t)k * kBlock + threadIdx.x);
+        const d2 x0 = d2{(double)sv[k].x, (double)sv[k].y}, x1 = d2{(double)sv[k].z, (double)sv[k].w};
+        d2 o0, o1;
+        if constexpr (MODE == 1) {
+          const d2 a0 = __builtin_bit_cast(d2, dv[k][0]), a1 = __builtin_bit_cast(d2, dv[k][1]);
+          o0 = d2{a0.x + x0.x, a0.y + x0.y};
+          o1 = d2{a1.x + x1.x, a1.y + x1.y};
+        } else if constexpr (MODE == 2) {
+          o0 = d2{0.0 + x0.x, 0.0 + x0.y};
+          o1 = d2{0.0 + x1.x, 0.0 + x1.y};
+        } else {
+          o0 = x0;
+          o1 = x1;
+        }
+        *(gu2)(dst + i) = encode2<BE_OUT>(o0);
+        *(gu2)(dst + i + 2) = encode2<BE_OUT>(o1);
+      }
+      return;
+    }
+    const int64_t end = base + kEwTile < L ? base + kEwTile : L;
+    for (int64_t i = base + threadIdx.x; i < end; i += kBlock) one(i);
+  } else {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < L) one(i);
+  }
+}
+
+// k_load_model over a float model (InitializeWeights from model.params()).
+__global__ __launch_bounds__(kBlock) void k_load_model_f32(const float* __restrict__ flat, int64_t lo, int64_t ncopy,
+                                                           int64_t L, double* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= L) return;
+  dst[i] = (i < ncopy) ? (double)ld4f(flat + lo + i) : 0.0;
+}
+
+// ---------------------------------------------------------------------------
+// k_divide_f32: the GetPartitions divide (k_divide) narrowed to float:
+//   out[m] = (float)(cnt == 0.0 ? W[p][j] : W[p][j] / den)
+// The quotient is k_divide's IEEE double division; it is rounded once to
+// float (ties to even; overflow to +-inf, subnormals kept, -0.0 stays -0.0).
+// Never an f32 division, never a reciprocal.  Tiles are laid over the OUTPUT
+// as in k_divide: block 0 writes the `head` floats up to the first 128-B line
+// of this partition's output (p*chunk floats is arbitrary mod 4), then every
+// lane stores 16 B = 4 floats and a wave whole lines (64 x 16 B = 8 lines); W
+// is read with 8-B loads (its alignment against the output is arbitrary).
+// ---------------------------------------------------------------------------
+constexpr int kDivV32 = 2;
+constexpr int64_t kDivTile32 = (int64_t)kBlock * 4 * kDivV32;
+
+template <bool SECURE, int BS = kBlock, int V = kDivV32>
+__global__ __launch_bounds__(BS) void k_divide_f32(const DivDesc* __restrict__ parts, const double* __restrict__ arena,
+                                                   float* __restrict__ out, int tiles_per_part) {
+  constexpr int64_t kTile = (int64_t)BS * 4 * V;
+  static_assert(BS % 64 == 0, "whole waves");
+  const int q = blockIdx.x / tiles_per_part;
+  const int t = blockIdx.x - q * tiles_per_part;
+  const DivDesc d = parts[q];
+  const int64_t n = d.len - 1;
+  const double* w = arena + d.w_off;
+  const double cnt = w[d.len - 1];
+  const double den = SECURE ? 1e12 * cnt : cnt;   // IPLS.java:1167
+  auto f = [&](double x) -> float { return (float)((cnt == 0.0) ? x : x / den); };
+  float* o = out + d.out_off;
+  const int64_t to_line = (32 - (int64_t)(((uintptr_t)o >> 2) & 31)) & 31;   // floats to a 128-B boundary
+  const int64_t head = to_line < n ? to_line : n;
+  if (t == 0 && threadIdx.x < head) o[threadIdx.x] = f(w[threadIdx.x]);
+  const int64_t base = (int64_t)t * kTile + head;
+  if (base >= n) return;
+  if (base + kTile <= n) {
+    // wave (threadIdx.x / 64) owns [base + wave * 256 * V, + 256 * V)
+    const int64_t wave_base = base + (int64_t)(threadIdx.x >> 6) * 256 * V + 4 * (threadIdx.x & 63);
+    double x[V][4];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int64_t i = wave_base + (int64_t)v * 256;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        x[v][c] = __builtin_nontemporal_load((const __attribute__((address_space(1))) double*)(w + i + c));
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int64_t i = wave_base + (int64_t)v * 256;
+      const f4 y = f4{f(x[v][0]), f(x[v][1]), f(x[v][2]), f(x[v][3])};
+      __builtin_nontemporal_store(y, (gf4)(o + i));
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < n; i += BS) o[i] = f(w[i]);
+}
+
 }  // namespace ipls

@@ -42,6 +42,11 @@ from . import _native as N
 class DeviceBuffer:
     """A device-resident operand: address, element count, big-endian or not.
 
+    ``dtype`` is ``"f64"`` (doubles, or big-endian double bytes) or ``"f32"``
+    (a trainer's float parameters or gradients, Model.java:423 / 388-390: the
+    library widens or narrows them on the device); ``n`` counts elements of
+    that dtype.
+
     The handle's HIP stream is non-blocking (include/ipls_agg.h): bytes
     written by torch or the null stream must be complete before the call
     that reads them (``torch.cuda.synchronize()``, or an event the handle's
@@ -49,28 +54,53 @@ class DeviceBuffer:
     ptr: int
     n: int
     big_endian: bool = False
+    dtype: str = "f64"
+
+    def __post_init__(self):
+        if self.dtype not in ("f64", "f32"):
+            raise ValueError(f"dtype must be 'f64' or 'f32', not {self.dtype!r}")
+        if self.dtype == "f32" and self.big_endian:
+            raise ValueError("big-endian buffers hold doubles: dtype='f32' cannot be big_endian")
 
     @classmethod
     def from_tensor(cls, t, big_endian: bool = False) -> "DeviceBuffer":
+        """A ``torch.float32`` tensor gives an f32 buffer of ``numel()``
+        elements; every other dtype is a carrier of 8-byte values (float64,
+        or uint8 / int64 holding doubles or big-endian double bytes)."""
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError("need a contiguous device tensor")
+        if str(t.dtype) == "torch.float32":
+            return cls(int(t.data_ptr()), t.numel(), big_endian, "f32")
         return cls(int(t.data_ptr()), t.numel() * t.element_size() // 8, big_endian)
 
     @property
     def kind(self) -> int:
+        if self.dtype == "f32":
+            return N.DEV_F32
         return N.DEV_BE if self.big_endian else N.DEV_F64
 
 
 def _bucket_table(buckets, lengths, p_first: int):
-    """(flat pointer list, k) of a batched call's bucket table: ``buckets[q]``
-    are the k device buckets of partition ``p_first + q``.  The C-ABI takes
-    bare pointers and reads L_p doubles from each (include/ipls_agg.h), so a
-    DeviceBuffer shorter than its partition is refused here, before any
-    launch could read past it.  Raw integer addresses are the caller's
-    contract; partitions out of range are left to the library's range check."""
+    """(flat pointer list, k) of a batched call's bucket table, with the checks
+    of _bucket_table_kind (lengths in elements, no mixing of f32 and f64)."""
+    return _bucket_table_kind(buckets, lengths, p_first)[:2]
+
+
+def _bucket_table_kind(buckets, lengths, p_first: int, big_endian: bool = False):
+    """(flat pointer list, k, src_kind) of a batched call's bucket table:
+    ``buckets[q]`` are the k device buckets of partition ``p_first + q``.  The
+    C-ABI takes bare pointers and reads L_p elements from each
+    (include/ipls_agg.h), so a DeviceBuffer shorter than its partition -- in
+    elements of its dtype -- is refused here, before any launch could read
+    past it.  The kind is DEV_F32 when the DeviceBuffers are f32 (one call
+    folds one kind: a table that mixes f32 and f64 buffers is refused), else
+    DEV_BE / DEV_F64 by ``big_endian``, which applies to f64 buckets only.
+    Raw integer addresses are the caller's contract; partitions out of range
+    are left to the library's range check."""
     n_parts = len(buckets)
     k = len(buckets[0]) if n_parts else 0
     flat = []
+    dtypes = set()
     for q, row in enumerate(buckets):
         if len(row) != k:
             raise ValueError("every partition needs the same number of buckets")
@@ -79,15 +109,25 @@ def _bucket_table(buckets, lengths, p_first: int):
         for b in row:
             if isinstance(b, DeviceBuffer):
                 if b.n < need:
-                    raise ValueError(f"partition {p} needs buckets of {need} doubles, a DeviceBuffer holds {b.n}")
+                    raise ValueError(f"partition {p} needs buckets of {need} "
+                                     f"{'floats' if b.dtype == 'f32' else 'doubles'}, a DeviceBuffer holds {b.n}")
+                dtypes.add(b.dtype)
                 flat.append(b.ptr)
             else:
                 flat.append(int(b))
-    return flat, k
+    if len(dtypes) > 1:
+        raise ValueError("a bucket table holds f32 or f64 DeviceBuffers, not both")
+    if dtypes == {"f32"}:
+        if big_endian:
+            raise ValueError("big_endian applies to f64 buckets only")
+        return flat, k, N.DEV_F32
+    return flat, k, (N.DEV_BE if big_endian else N.DEV_F64)
 
 
-def _host_operand(x, big_endian: bool):
-    """(pointer, n_doubles, kind, keepalive) for a host operand."""
+def _host_operand(x, big_endian: bool, f32: bool = False):
+    """(pointer, n_elements, kind, keepalive) for a host operand.  ``f32``: the
+    call takes HOST_F32 (include/ipls_agg.h), so a numpy float32 array goes as
+    it is and is widened on the device; elsewhere it is widened here."""
     if isinstance(x, (bytes, bytearray, memoryview)):
         a = np.frombuffer(x, dtype=np.uint8)
     else:
@@ -98,14 +138,17 @@ def _host_operand(x, big_endian: bool):
     if a.dtype.byteorder == ">":
         a = np.ascontiguousarray(a)
         return a.ctypes.data, a.size, N.HOST_BE, a
+    if f32 and a.dtype == np.float32:   # a trainer's floats: 4 B per element to the device, widened there
+        a = np.ascontiguousarray(a)
+        return a.ctypes.data, a.size, N.HOST_F32, a
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a.ctypes.data, a.size, N.HOST_F64, a
 
 
-def _operand(x, big_endian: bool = False):
+def _operand(x, big_endian: bool = False, f32: bool = False):
     if isinstance(x, DeviceBuffer):
         return x.ptr, x.n, x.kind, x
-    return _host_operand(x, big_endian)
+    return _host_operand(x, big_endian, f32)
 
 
 def _callback(caught: list, fn, *args) -> int:
@@ -221,12 +264,12 @@ class Aggregator:
             keep = _u8(model)
             ptr, n, kind = keep.ctypes.data, keep.size, N.HOST_DLIST
         else:
-            ptr, n, kind, keep = _operand(model, big_endian)
+            ptr, n, kind, keep = _operand(model, big_endian, f32=True)
         self._chk(self._lib.ipls_agg_load_model(self._h, ptr, n, kind))
 
     def OrganizeGradients(self, gradients, big_endian_out: bool = False) -> dict[int, np.ndarray]:
         """IPLS.java:1018-1040: {p: double[L_p]} with the count slot 1.0."""
-        ptr, n, kind, keep = _operand(gradients)
+        ptr, n, kind, keep = _operand(gradients, f32=True)
         out = {}
         for p in range(self.n_partitions):
             L = self.lengths[p]
@@ -246,7 +289,7 @@ class Aggregator:
         owned = np.ascontiguousarray(np.asarray(list(auth_list), dtype=np.int32))
         if gradients is None:
             return
-        ptr, n, kind, keep = _operand(gradients)
+        ptr, n, kind, keep = _operand(gradients, f32=True)
         self._chk(self._lib.ipls_agg_update_gradient(
             self._h, ptr, n, kind, owned.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(owned)))
 
@@ -267,7 +310,7 @@ class Aggregator:
             self._chk(self._lib.ipls_agg_accumulate(self._h, partition, target, a.ctypes.data,
                                                     a.size, N.HOST_PAIR if pair else N.HOST_FRAME))
             return
-        ptr, n, kind, keep = _operand(gradient)
+        ptr, n, kind, keep = _operand(gradient, f32=True)
         if self._fast is not None:
             rc = self._fast.accumulate(self._hv, partition, target, ptr, n, kind)
             if rc < 0:
@@ -283,15 +326,14 @@ class Aggregator:
         a ticket; keep the buffer until Wait(ticket)."""
         target = N.TGT_AGG if from_clients else N.TGT_REP
         if self._fast is not None and isinstance(gradient, DeviceBuffer):
-            t = self._fast.accumulate_async(self._hv, partition, target, gradient.ptr, gradient.n,
-                                            N.DEV_BE if gradient.big_endian else N.DEV_F64)
+            t = self._fast.accumulate_async(self._hv, partition, target, gradient.ptr, gradient.n, gradient.kind)
             if t < 0:
                 self._chk(t)
             return t
         t = ctypes.c_uint64()
         if isinstance(gradient, DeviceBuffer):
             rc = self._lib.ipls_agg_accumulate_async(self._h, partition, target, gradient.ptr, gradient.n,
-                                                     N.DEV_BE if gradient.big_endian else N.DEV_F64, ctypes.byref(t))
+                                                     gradient.kind, ctypes.byref(t))
             if rc < 0:
                 self._chk(rc)
             return t.value
@@ -321,7 +363,7 @@ class Aggregator:
         items = []
         for g, p in arrivals:
             if isinstance(g, DeviceBuffer):
-                items.append((p, g.ptr, g.n, N.DEV_BE if g.big_endian else N.DEV_F64))
+                items.append((p, g.ptr, g.n, g.kind))
             elif isinstance(g, PinnedBuffer):
                 items.append((p, g.ptr, g.nbytes // 8, N.HOST_BE if big_endian else N.HOST_F64))
             else:
@@ -510,9 +552,8 @@ class Aggregator:
         """One launch over len(buckets) partitions; buckets[q] is the list of
         device pointers (ints or DeviceBuffers) for partition p_first+q."""
         n_parts = len(buckets)
-        flat, k = _bucket_table(buckets, self.lengths, p_first)
+        flat, k, kind = _bucket_table_kind(buckets, self.lengths, p_first, big_endian)
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
-        kind = N.DEV_BE if big_endian else N.DEV_F64
         self._chk(self._lib.ipls_agg_reduce_batch(self._h, p_first, n_parts, arr, k, kind,
                                                   start_mode, target))
 
@@ -523,42 +564,47 @@ class Aggregator:
         n_parts = len(buckets)
         if len(dsts) != n_parts:
             raise ValueError("need k buckets and one destination per partition")
-        flat, k = _bucket_table(buckets, self.lengths, p_first)
+        flat, k, kind = _bucket_table_kind(buckets, self.lengths, p_first, big_endian_in)
         for q, d in enumerate(dsts):
             p = p_first + q
+            if isinstance(d, DeviceBuffer) and d.dtype == "f32":
+                raise N.IplsError(N.IPLS_E_INVAL, "reduce_batch_out writes doubles or big-endian bytes, not f32")
             if isinstance(d, DeviceBuffer) and 0 <= p < self.n_partitions and d.n < self.lengths[p]:
                 raise ValueError(f"partition {p} needs a destination of {self.lengths[p]} doubles, "
                                  f"the DeviceBuffer holds {d.n}")
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
         darr = (ctypes.c_void_p * max(1, n_parts))(*[d.ptr if isinstance(d, DeviceBuffer) else int(d) for d in dsts])
         self._chk(self._lib.ipls_agg_reduce_batch_out(
-            self._h, p_first, n_parts, arr, k, N.DEV_BE if big_endian_in else N.DEV_F64, start_mode,
+            self._h, p_first, n_parts, arr, k, kind, start_mode,
             darr, N.DEV_BE if big_endian_out else N.DEV_F64))
 
     def aggregate_round(self, p_first: int, buckets, *, big_endian: bool = False, with_average: bool = True,
-                        out=None):
+                        out=None, dtype=np.float64):
         """A whole round in one launch: the folds of ``buckets`` (buckets[q] =
         device buckets of partition p_first+q, may be empty lists) into AGG,
         AggregatePartition (IPLS.java:1248-1274) and the GetPartitions divide
         (IPLS.java:1159-1174).  Returns the averaged values of the partitions
-        (host array, or ``out`` when a DeviceBuffer is given), or None."""
+        (host array, or ``out`` when a DeviceBuffer is given), or None.
+        f32 buckets are widened in the fold; an f32 ``out`` (or
+        ``dtype=np.float32`` for the host array) gets the averages narrowed
+        once to float, as Model.java:388-390 narrows them."""
         n_parts = len(buckets)
-        flat, k = _bucket_table(buckets, self.lengths, p_first)
+        flat, k, kind = _bucket_table_kind(buckets, self.lengths, p_first, big_endian)
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
-        kind = N.DEV_BE if big_endian else N.DEV_F64
         ap, ak, res = None, N.HOST_F64, None
         if isinstance(out, DeviceBuffer):
             if n_parts and 0 <= p_first and p_first + n_parts <= self.n_partitions:
                 last = p_first + n_parts - 1
                 need = self.offsets[last] + self.lengths[last] - 1 - self.offsets[p_first]
                 if out.n < need:
-                    raise ValueError(f"the averages of partitions {p_first}..{last} need {need} doubles, "
+                    raise ValueError(f"the averages of partitions {p_first}..{last} need {need} values, "
                                      f"the DeviceBuffer holds {out.n}")
-            ap, ak, res = out.ptr, N.DEV_F64, out
+            ap, ak, res = out.ptr, (N.DEV_F32 if out.dtype == "f32" else N.DEV_F64), out
         elif with_average:
             last = p_first + n_parts - 1
             n = self.offsets[last] + self.lengths[last] - 1 - self.offsets[p_first]
-            res = np.empty(max(0, n))
+            res = np.empty(max(0, n), dtype=np.float32 if np.dtype(dtype) == np.float32 else np.float64)
+            ak = N.HOST_F32 if res.dtype == np.float32 else N.HOST_F64
             ap = res.ctypes.data if res.size else None
         self._chk(self._lib.ipls_agg_aggregate_round(self._h, p_first, n_parts, arr, k, kind, ap, ak))
         return res
@@ -693,16 +739,23 @@ class Aggregator:
         ptr, n, kind, keep = _operand(data)
         self._chk(self._lib.ipls_agg_set_weights(self._h, partition, ptr, n, kind))
 
-    def GetPartitions(self, *, wire: bool = False, out=None):
+    def GetPartitions(self, *, wire: bool = False, out=None, dtype=np.float64):
         """IPLS.java:1140-1174: the averaged flat model.  ``wire=True`` returns
         the Middleware task-3 byte stream (DataOutputStream.writeDouble);
         with ``out`` a PinnedBuffer it is written there (the D2H at the PCIe
         rate) and a memoryview of those 8*M bytes is returned, ready for
-        ``sendall`` without another copy."""
+        ``sendall`` without another copy.  An f32 DeviceBuffer ``out``, or
+        ``dtype=np.float32`` for the host array, gets every value rounded once
+        to float on the device (Model.java:388-390), 4 bytes per value."""
         n = self.flat_size
         if isinstance(out, DeviceBuffer):
-            self._chk(self._lib.ipls_agg_get_partitions(self._h, out.ptr, out.n, N.DEV_F64))
+            self._chk(self._lib.ipls_agg_get_partitions(self._h, out.ptr, out.n,
+                                                        N.DEV_F32 if out.dtype == "f32" else N.DEV_F64))
             return out
+        if np.dtype(dtype) == np.float32 and out is None and not wire:
+            buf = np.empty(n, dtype=np.float32)
+            self._chk(self._lib.ipls_agg_get_partitions(self._h, buf.ctypes.data, n, N.HOST_F32))
+            return buf
         if isinstance(out, PinnedBuffer):
             if out.nbytes < 8 * n:
                 raise ValueError(f"PinnedBuffer of {out.nbytes} bytes < the model's {8 * n}")
@@ -761,7 +814,9 @@ class Aggregator:
         folds buckets resident on its GPU into its partial sums (an aggregator
         of the partition other than its owner, IPLS.java:1402-1431)."""
         n_parts = len(buckets)
-        flat, k = _bucket_table(buckets, self.lengths, p_first)
+        flat, k, bk = _bucket_table_kind(buckets, self.lengths, p_first)
+        if bk == N.DEV_F32:
+            raise N.IplsError(N.IPLS_E_INVAL, "reduce_partial takes f64 buckets (DEV_F64/DEV_BE)")
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
         self._chk(self._lib.ipls_agg_reduce_partial(self._h, slot, p_first, n_parts, arr, k,
                                                     N.DEV_BE if big_endian else N.DEV_F64, start_mode))
