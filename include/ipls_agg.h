@@ -127,6 +127,37 @@ extern "C" {
  * copied, not read zero-copy). */
 #define IPLS_DEV_F32     11  /* device float*, 4-byte aligned                                 */
 #define IPLS_HOST_F32    12  /* host float[] (native byte order)                              */
+/* The half-precision trainer boundary: the same two lines of Model.java with a 2-byte
+ * INDArray (a DL4J network built with DataType.HALF or BFLOAT16), or a PyTorch trainer
+ * under autocast whose parameters and gradients are torch.float16 / torch.bfloat16.
+ *   Sources (widening rule): v = (double)src[i], then exactly what the F64 kind does, so
+ * the bits are those of the F64 call fed the widened values.  IEEE binary16 is widened
+ * f16 -> f32 -> f64 (both steps exact, f16 subnormals kept); bfloat16 is (bits << 16) taken
+ * as an f32, then -> f64 (exact; a bf16 subnormal is an f32 subnormal and is kept).  Signs
+ * and +-0 are kept, infinities stay infinities, a quiet NaN gives a NaN (what a signalling
+ * NaN's payload becomes is unspecified).  No flush-to-zero anywhere.
+ *   Outputs (two-step narrowing rule): the IEEE double quotient of GetPartitions (secure
+ * mode included) is FIRST rounded to float exactly as the F32 kind does (one round to
+ * nearest even), THEN that float is rounded to the 16-bit format: ties to even, overflow
+ * to +-inf, subnormal results kept, -0.0 stays -0.0, NaN stays a NaN.  So an F16 / BF16
+ * output equals the F32 output narrowed by the trainer (numpy's astype(float16), torch's
+ * .to(bfloat16)).  This is deliberately NOT a single rounding of the double: a quotient
+ * of 1 + 2^-11 + 2^-30 gives the half 0x3c00 (a single rounding would give 0x3c01),
+ * 1 + 2^-8 + 2^-30 the bfloat16 0x3f80 (not 0x3f81).  It is what a trainer gets today
+ * when it narrows the F32 output itself, and it keeps the three output kinds consistent.
+ *   n counts ELEMENTS; a count slot of a 16-bit bucket is 1.0 in that format.  The kinds
+ * are accepted where the F32 kinds are and nowhere else:
+ *   sources: ipls_agg_update_gradient, ipls_agg_split (src), ipls_agg_load_model,
+ *            ipls_agg_accumulate, ipls_agg_accumulate_async (DEV and HOST kinds);
+ *            ipls_agg_reduce_batch, ipls_agg_reduce_batch_out, ipls_agg_aggregate_round
+ *            (bufs: the DEV kinds; the destinations stay F64 / BE)
+ *   outputs: ipls_agg_get_partitions (out_kind), ipls_agg_aggregate_round (avg_kind)
+ * Every other call refuses them with IPLS_E_INVAL, as it refuses F32.  A HOST operand
+ * crosses PCIe as 2 B per element (pinned ones too: copied, not read zero-copy). */
+#define IPLS_DEV_F16     13  /* device IEEE binary16[], 2-byte aligned                        */
+#define IPLS_HOST_F16    14  /* host IEEE binary16[] (native byte order)                      */
+#define IPLS_DEV_BF16    15  /* device bfloat16[], 2-byte aligned                             */
+#define IPLS_HOST_BF16   16  /* host bfloat16[] (native byte order)                           */
 
 /* ---- ipls_agg_load_saved modes ---- */
 #define IPLS_SAVED_SET    0  /* target[p] = file[p]                                          */
@@ -654,6 +685,9 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
 #define IPLS_KERNEL_REDUCE_SCALAR 4  /* k_reduce_scalar */
 #define IPLS_KERNEL_REDUCE_F32    5  /* k_reduce_f32: DEV_F32 buckets; a tile is block x 4 x vectors
                                         elements; shape 0; seqf 1 when every operand was 16-B
+                                        aligned (vector path), 0 for the element-by-element form */
+#define IPLS_KERNEL_REDUCE_H16    6  /* k_reduce_h16: DEV_F16 / DEV_BF16 buckets; a tile is block x 4 x
+                                        vectors elements; shape 0; seqf 1 when every operand was 16-B
                                         aligned (vector path), 0 for the element-by-element form */
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2

@@ -88,6 +88,27 @@ struct ipls_stage {
   bool free_pending = false;
 };
 
+// Element format of a source or an output: native doubles, big-endian double
+// bytes, or one of the trainer formats of include/ipls_agg.h (floats, IEEE
+// binary16, bfloat16), which the kernels widen / narrow in registers.  The
+// values are also the format codes of the accumulate_async queues.
+enum Fmt : int { kFmtF64 = 0, kFmtBE = 1, kFmtF32 = 2, kFmtF16 = 3, kFmtBF16 = 4 };
+constexpr Fmt be_fmt(bool be) { return be ? kFmtBE : kFmtF64; }
+constexpr bool fmt_trainer(Fmt f) { return f >= kFmtF32; }                    // widened on the device
+constexpr bool fmt_h16(Fmt f) { return f == kFmtF16 || f == kFmtBF16; }
+constexpr int fmt_size(Fmt f) { return f == kFmtF32 ? 4 : fmt_h16(f) ? 2 : 8; }   // bytes per element (= alignment)
+// format of an operand kind where the trainer kinds are accepted; every other kind counts as doubles
+constexpr Fmt kind_fmt(int kind) {
+  return kind == IPLS_DEV_BE || kind == IPLS_HOST_BE                ? kFmtBE
+         : kind == IPLS_DEV_F32 || kind == IPLS_HOST_F32            ? kFmtF32
+         : kind == IPLS_DEV_F16 || kind == IPLS_HOST_F16            ? kFmtF16
+         : kind == IPLS_DEV_BF16 || kind == IPLS_HOST_BF16          ? kFmtBF16
+                                                                    : kFmtF64;
+}
+constexpr bool kind_trainer_dev(int kind) { return kind == IPLS_DEV_F32 || kind == IPLS_DEV_F16 || kind == IPLS_DEV_BF16; }
+constexpr bool kind_trainer_host(int kind) { return kind == IPLS_HOST_F32 || kind == IPLS_HOST_F16 || kind == IPLS_HOST_BF16; }
+constexpr bool kind_trainer(int kind) { return kind_trainer_dev(kind) || kind_trainer_host(kind); }
+
 struct ipls_dev {
   std::mutex mu;
   std::string err;
@@ -151,7 +172,7 @@ struct ipls_dev {
   // first (IPLS_LOCK).  Pinned host buckets fold at once (zero copy).
   struct Pending {
     std::vector<const void*> bufs;
-    int fmt = 0;   // the queue's bucket format: 0 native doubles, 1 big-endian, 2 floats (DEV_F32)
+    Fmt fmt = kFmtF64;   // the queue's bucket format (one per queue)
   };
   // queue of (target, p) at pend[target * P + p]; pend_keys lists the
   // non-empty ones (a flat table: the per-arrival call is a few loads and a
@@ -871,6 +892,54 @@ ipls_launch_info launch_reduce_f32(bool be_out, int start, bool vec, int64_t max
                      be_out, start);
 }
 
+// ---- kernel dispatch: k_reduce_h16 (DEV_F16 / DEV_BF16 buckets) ----
+// One shape for every grid: layout A of the sweep -- 8-B loads, kH16E = 4
+// elements per lane per vector, k_reduce_f32's lane ^ 4 swap before the stores
+// -- on 1024-lane workgroups with 4 vectors per lane (32 KiB of a bucket per
+// block, 32 accumulator VGPRs), the next peer's 4 loads issued before this
+// peer's values are added (68-90 VGPRs over the start modes, no scratch).
+// Same process, same buckets, single launches, sums 128-B aligned as in the
+// arena (tools/reduce_h16_sweep.hip, profiles/h16_boundary/sweep_*.txt).  At
+// config C's 16 x 4M x 32 three shapes are level: this one 0.781-0.796 ms
+// (75.9-77.4 % of 8 TB/s), layout A's 512 x 2 0.791-0.792 ms, and layout B
+// (16-B loads, 8 elements per lane, pairs transposed across 8 lanes) at
+// 512 x 2 without the prefetch 0.771-0.799 ms, the fastest row for halves.
+// 1 x 4M x 32 decides: this shape 77.2 % (level with the column's best, B's
+// 1024 x 2 with the prefetch, 77.4 %, which has 73.3-73.7 % at config C)
+// against 69.2 % for B's 512 x 2 and 64.5 % for A's 512 x 2.  ETHModel's
+// 3 x 147,870 x 3 takes 7.5 us against 6.6 us for the tiles of 8,192 elements
+// and below (30 blocks instead of 57 or more).  Both layouts write 1.0000x the algorithmic bytes; without
+// the exchange A writes 1.114x and B 1.56-1.59x (pmc_sweep_WRITE_SIZE.csv).
+// Partial last tiles are scheduled first (map 3) as for k_reduce.  vec: every
+// bucket and destination is 16-B aligned; otherwise the same grid runs element
+// by element.
+constexpr int kH16BS = 1024, kH16R = 4, kH16PF = 1, kH16E = 4;
+template <class H>
+ipls_launch_info launch_reduce_h16(bool be_out, int start, bool vec, int64_t maxL, int n_parts, hipStream_t st,
+                                   const unsigned short* const* bufs, const PartDesc* parts, int k) {
+  const int64_t tile = (int64_t)kH16BS * kH16E * kH16R;
+  const int64_t tpp = (maxL + tile - 1) / tile;
+  const bool partial = tpp > 1 && maxL % tile != 0;
+  const dim3 grid((unsigned)(tpp * n_parts));
+#define RH(BO, ST, MAP, V)                                                                                       \
+  hipLaunchKernelGGL((k_reduce_h16<H, BO, ST, kH16R, kH16BS, MAP, V, (V ? kH16PF : 0), kH16E>), grid, dim3(kH16BS), \
+                     0, st, bufs, parts, k, (int)tpp, n_parts)
+#define RH3(BO, ST)                                         \
+  do {                                                      \
+    if (!vec) RH(BO, ST, 0, false);                         \
+    else if (partial) RH(BO, ST, 3, true);                  \
+    else RH(BO, ST, 0, true);                               \
+  } while (0)
+#define RH2(BO) do { if (start == kZero) RH3(BO, kZero); else if (start == kFirst) RH3(BO, kFirst); else RH3(BO, kAccum); } while (0)
+  if (be_out) RH2(true);
+  else RH2(false);
+#undef RH2
+#undef RH3
+#undef RH
+  return launch_info(IPLS_KERNEL_REDUCE_H16, 0, kH16BS, kH16R, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false,
+                     be_out, start);
+}
+
 // Core of accumulate / reduce_batch: all pointers device-resident.  The
 // destination is the handle's `target` accumulators, or -- when ext_dst is
 // given -- one caller buffer per partition (doubles or, be_out, BE bytes).
@@ -884,11 +953,12 @@ struct FinOut {
 // host_src: the bucket is pinned host memory read over PCIe (zero copy); the
 // single-bucket fold then runs on 128 workgroups, which measured 1-2.5 GB/s
 // above 256..4096 (tools/h2d_bench.hip, profiles/r01/h2d_bench_fold1.txt).
-int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, int k, bool be_in,
+int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, int k, Fmt fmt_in,
                int start_mode, int target, void* const* ext_dst = nullptr, bool be_out = false,
-               const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr,
-               bool f32_in = false) {
-  // f32_in: the buckets hold floats (DEV_F32), 4-B aligned; never with be_in or fin
+               const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr) {
+  // fmt_in: what the buckets hold.  The trainer formats (floats, halves,
+  // bfloat16s) are aligned to their element size and never come with fin.
+  const bool be_in = fmt_in == kFmtBE, tr_in = fmt_trainer(fmt_in);
   // lens: lengths of caller destinations that are not this engine's
   // partitions (ext_dst only, e.g. a replica slot's partial sums)
   auto len_of = [&](int q) -> int64_t { return lens ? lens[q] : h->len[p_first + q]; };
@@ -926,7 +996,7 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   }
   // one bucket into one partition (every per-arrival fold): pointers go as
   // kernel arguments, no table upload
-  if (!fin && !f32_in && n_parts == 1 && k == 1 && bufs[0]) {
+  if (!fin && !tr_in && n_parts == 1 && k == 1 && bufs[0]) {
     unsigned long long* d0 = dst_of(0);
     const int64_t L = len_of(0);
     if (d0 && !((uintptr_t)bufs[0] & 15) && !((uintptr_t)d0 & 15) && L > 0) {
@@ -952,8 +1022,8 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   for (int64_t i = 0; i < (int64_t)n_parts * k; ++i) {
     if (!bufs[i]) return fail(h, IPLS_E_INVAL, "bucket pointer %lld is NULL", (long long)i);
     uintptr_t a = (uintptr_t)bufs[i];
-    if (a & (f32_in ? 3 : 7))
-      return fail(h, IPLS_E_INVAL, "bucket %lld not %d-byte aligned", (long long)i, f32_in ? 4 : 8);
+    if (a & (uintptr_t)(fmt_size(fmt_in) - 1))
+      return fail(h, IPLS_E_INVAL, "bucket %lld not %d-byte aligned", (long long)i, fmt_size(fmt_in));
     if (a & 15) aligned16 = false;
   }
   // table = [PartDesc x n_parts][ptr x n_parts*k]
@@ -984,15 +1054,21 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   const PartDesc* dparts = (const PartDesc*)dtab;
   auto dbufs = (const unsigned long long* const*)((char*)dtab + desc_bytes);
   if (fin) {
-    if (!aligned16 || f32_in) return fail(h, IPLS_E_INVAL, "fused round needs 16-B aligned F64/BE buckets");
+    if (!aligned16 || tr_in) return fail(h, IPLS_E_INVAL, "fused round needs 16-B aligned F64/BE buckets");
     h->last_launch = launch_reduce_fin(be_in, start, h->secure, maxL, n_parts, h->stream, dbufs, dparts, k, h->d_cnt);
     HIP_TRY(h, hipGetLastError());
     for (int q = p_first; q < p_first + n_parts; ++q) h->agg_zero[q] = h->rep_zero[q] = 1;
     return IPLS_OK;
   }
-  if (f32_in) {
+  if (fmt_in == kFmtF32) {
     h->last_launch = launch_reduce_f32(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
                                        (const float* const*)dbufs, dparts, k);
+  } else if (fmt_in == kFmtF16) {
+    h->last_launch = launch_reduce_h16<FmtF16>(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
+                                               (const unsigned short* const*)dbufs, dparts, k);
+  } else if (fmt_in == kFmtBF16) {
+    h->last_launch = launch_reduce_h16<FmtBF16>(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
+                                                (const unsigned short* const*)dbufs, dparts, k);
   } else if (aligned16) {
     h->last_launch = launch_reduce(be_in, be_out, start, maxL, n_parts, h->stream, dbufs, dparts, k);
   } else {
@@ -1323,8 +1399,7 @@ int flush_pending(ipls_dev* h) {
     }
     tab.clear();
     for (size_t t = i; t < j; ++t) tab.insert(tab.end(), h->pend[keys[t]].bufs.begin(), h->pend[keys[t]].bufs.end());
-    rc = reduce_dev(h, p0, n, tab.data(), (int)k, q0.fmt == 1, IPLS_START_ACCUM, target, nullptr, false, nullptr, false,
-                    nullptr, q0.fmt == 2);
+    rc = reduce_dev(h, p0, n, tab.data(), (int)k, q0.fmt, IPLS_START_ACCUM, target);
     i = j;
   }
   for (int key : keys) h->pend[key].bufs.clear();   // keeps the capacity
@@ -1342,14 +1417,13 @@ int dev_reduce_batch(ipls_dev* h, int p_first, int n_parts, const void* const* b
   IPLS_LOCK(h);
   if (n_parts <= 0 || p_first < 0 || p_first + n_parts > h->P)
     return fail(h, IPLS_E_RANGE, "partitions [%d,%d) out of range [0,%d)", p_first, p_first + n_parts, h->P);
-  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && src_kind != IPLS_DEV_F32)
-    return fail(h, IPLS_E_INVAL, "reduce_batch takes device buckets (DEV_F64/DEV_BE/DEV_F32)");
+  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && !kind_trainer_dev(src_kind))
+    return fail(h, IPLS_E_INVAL, "reduce_batch takes device buckets (DEV_F64/DEV_BE/DEV_F32/DEV_F16/DEV_BF16)");
   if (start_mode < IPLS_START_ACCUM || start_mode > IPLS_START_FIRST) return fail(h, IPLS_E_INVAL, "bad start mode");
   if (target_off(h, 0, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
   if (k < 0 || (k > 0 && !bufs)) return fail(h, IPLS_E_INVAL, "bad bucket list");
   HIP_TRY(h, dev_use(h->device));
-  return reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, start_mode, target, nullptr, false, nullptr,
-                    false, nullptr, src_kind == IPLS_DEV_F32);
+  return reduce_dev(h, p_first, n_parts, bufs, k, kind_fmt(src_kind), start_mode, target);
 }
 
 int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, int src_kind) {
@@ -1361,7 +1435,8 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
   HIP_TRY(h, dev_use(h->device));
   const int64_t L = h->len[p];
   const void* dptr = nullptr;
-  bool be = false, staged = false, f32 = false;
+  bool be = false, staged = false;
+  Fmt tr = kFmtF64;   // a trainer format (floats, halves, bfloat16s), else doubles by `be`
   switch (src_kind) {
     case IPLS_DEV_F64:
     case IPLS_DEV_BE:
@@ -1379,7 +1454,7 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
         // staging copy, no second pass).  The call returns once the kernel
         // is done with the caller's bytes.
         const void* bl[1] = {alias};
-        if (int rc = reduce_dev(h, p, 1, bl, 1, be, IPLS_START_ACCUM, target, nullptr, false, nullptr, true))
+        if (int rc = reduce_dev(h, p, 1, bl, 1, be_fmt(be), IPLS_START_ACCUM, target, nullptr, false, nullptr, true))
           return rc;
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return IPLS_OK;
@@ -1389,18 +1464,25 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
       break;
     }
     case IPLS_DEV_F32:
-      // a co-located trainer's float bucket, widened in the fold (Model.java:423)
+    case IPLS_DEV_F16:
+    case IPLS_DEV_BF16:
+      // a co-located trainer's float / half / bfloat16 bucket, widened in the fold (Model.java:423)
+      tr = kind_fmt(src_kind);
       if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
-      if ((uintptr_t)src & 3) return fail(h, IPLS_E_INVAL, "device bucket not 4-byte aligned");
+      if ((uintptr_t)src & (uintptr_t)(fmt_size(tr) - 1))
+        return fail(h, IPLS_E_INVAL, "device bucket not %d-byte aligned", fmt_size(tr));
       dptr = src;
-      f32 = true;
       break;
     case IPLS_HOST_F32:
-      // 4 B per element cross PCIe; the widening happens on the device
+    case IPLS_HOST_F16:
+    case IPLS_HOST_BF16:
+      // 4 or 2 B per element cross PCIe; the widening happens on the device
+      tr = kind_fmt(src_kind);
       if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
-      if ((uintptr_t)src & 3) return fail(h, IPLS_E_INVAL, "host float bucket not 4-byte aligned");
-      if (int rc = stage_bucket(h, src, (size_t)L * 4, &dptr)) return rc;
-      staged = f32 = true;
+      if ((uintptr_t)src & (uintptr_t)(fmt_size(tr) - 1))
+        return fail(h, IPLS_E_INVAL, "host bucket not %d-byte aligned", fmt_size(tr));
+      if (int rc = stage_bucket(h, src, (size_t)L * fmt_size(tr), &dptr)) return rc;
+      staged = true;
       break;
     case IPLS_HOST_FRAME: {
       int16_t pid;
@@ -1445,27 +1527,26 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
       return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
   }
   const void* bl[1] = {dptr};
-  if (int rc = reduce_dev(h, p, 1, bl, 1, be, IPLS_START_ACCUM, target, nullptr, false, nullptr, false, nullptr, f32))
-    return rc;
+  if (int rc = reduce_dev(h, p, 1, bl, 1, fmt_trainer(tr) ? tr : be_fmt(be), IPLS_START_ACCUM, target)) return rc;
   return staged ? release_stage(h) : IPLS_OK;
 }
 
 int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_t n, int src_kind,
                               uint64_t* ticket) {
   if (!h || !ticket) return fail(h, IPLS_E_INVAL, "null argument");
-  if (src && (src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE || src_kind == IPLS_DEV_F32)) {
+  if (src && (src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE || kind_trainer_dev(src_kind))) {
     // device bucket: queued, folded with the partition's other queued buckets
     // (a queue holds one format: a bucket of another one flushes first, so
-    // call order is kept across F64, BE and F32 arrivals)
+    // call order is kept across F64, BE, F32, F16 and BF16 arrivals)
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = check_part(h, p)) return rc;
     if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
     if (n < h->len[p])
       return fail(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n,
                   (long long)h->len[p]);
-    const int fmt = src_kind == IPLS_DEV_BE ? 1 : src_kind == IPLS_DEV_F32 ? 2 : 0;
-    if ((uintptr_t)src & (fmt == 2 ? 3 : 7))
-      return fail(h, IPLS_E_INVAL, "device bucket not %d-byte aligned", fmt == 2 ? 4 : 8);
+    const Fmt fmt = kind_fmt(src_kind);
+    if ((uintptr_t)src & (uintptr_t)(fmt_size(fmt) - 1))
+      return fail(h, IPLS_E_INVAL, "device bucket not %d-byte aligned", fmt_size(fmt));
     // Weights and Weight_Address are one array (IPLS.java:1141): one queue
     const int qt = target == IPLS_TGT_WADDR ? IPLS_TGT_WEIGHTS : target;
     if (h->pend.empty()) h->pend.resize((size_t)5 * h->P);   // 5 targets (include/ipls_agg.h)
@@ -1498,7 +1579,7 @@ int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_
   if (int rc = host_decode_count(src_kind, n, h->len[p], h)) return rc;
   HIP_TRY(h, dev_use(h->device));
   const void* bl[1] = {alias};   // zero copy: the kernel reads the pinned bucket over PCIe
-  if (int rc = reduce_dev(h, p, 1, bl, 1, src_kind == IPLS_HOST_BE, IPLS_START_ACCUM, target, nullptr, false, nullptr,
+  if (int rc = reduce_dev(h, p, 1, bl, 1, be_fmt(src_kind == IPLS_HOST_BE), IPLS_START_ACCUM, target, nullptr, false, nullptr,
                           true))
     return rc;
   *ticket = h->ticket_next++;
@@ -1622,7 +1703,7 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
       }
     }
     const void* bl[1] = {d_in};
-    if (!rc) rc = reduce_dev(h, p, 1, bl, 1, src_kind == IPLS_HOST_BE, IPLS_START_ACCUM, target);
+    if (!rc) rc = reduce_dev(h, p, 1, bl, 1, be_fmt(src_kind == IPLS_HOST_BE), IPLS_START_ACCUM, target);
     // whatever ran, nothing queued on the shard stream after this point reads `d`
     if (hipEventRecord(st->free_ev, h->stream) == hipSuccess) {
       st->free_pending = true;
@@ -1794,7 +1875,7 @@ int dev_update_indirect(ipls_dev* h, int p, int target, const void* bytes, int64
     return fail(h, IPLS_E_RANGE, "partition length %lld > Gradient_Buff length %lld", (long long)h->len[p],
                 (long long)G);
   const void* bl[1] = {h->d_gbuf};
-  if (int rc = reduce_dev(h, p, 1, bl, 1, false, IPLS_START_ACCUM, target)) return rc;
+  if (int rc = reduce_dev(h, p, 1, bl, 1, kFmtF64, IPLS_START_ACCUM, target)) return rc;
   if (zero_copy) HIP_TRY(h, hipStreamSynchronize(h->stream));
   return IPLS_OK;
 }
@@ -1963,8 +2044,9 @@ static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, 
   return IPLS_OK;
 }
 
-// The same divide narrowed to float (k_divide_f32): d_out holds floats.
-static int divide_range_f32(ipls_dev* h, int p0, int np, float* d_out) {
+// The same divide narrowed to a trainer format: d_out holds floats
+// (k_divide_f32), halves or bfloat16s (k_divide_h16).
+static int divide_range_narrow(ipls_dev* h, int p0, int np, void* d_out, Fmt fmt) {
   std::vector<DivDesc> dd(np);
   int64_t maxn = 0;
   for (int q = 0; q < np; ++q) {
@@ -1975,14 +2057,22 @@ static int divide_range_f32(ipls_dev* h, int p0, int np, float* d_out) {
   if (maxn <= 0) return IPLS_OK;
   void* dtab = nullptr;
   if (int rc = upload_table(h, dd.data(), dd.size() * sizeof(DivDesc), &dtab)) return rc;
-  const int tpp = (int)((maxn + kDivTile32 - 1) / kDivTile32);
+  const int64_t tile = fmt == kFmtF32 ? kDivTile32 : kDivTile16;
+  const int tpp = (int)((maxn + tile - 1) / tile);
   const dim3 g((unsigned)tpp * np);
-  if (h->secure)
-    hipLaunchKernelGGL((k_divide_f32<true>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena,
-                       d_out, tpp);
-  else
-    hipLaunchKernelGGL((k_divide_f32<false>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena,
-                       d_out, tpp);
+#define DIVN(KERNEL, T)                                                                                          \
+  hipLaunchKernelGGL(KERNEL, g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena, (T*)d_out, tpp)
+  if (fmt == kFmtF32) {
+    if (h->secure) DIVN((k_divide_f32<true>), float);
+    else DIVN((k_divide_f32<false>), float);
+  } else if (fmt == kFmtF16) {
+    if (h->secure) DIVN((k_divide_h16<FmtF16, true>), unsigned short);
+    else DIVN((k_divide_h16<FmtF16, false>), unsigned short);
+  } else {
+    if (h->secure) DIVN((k_divide_h16<FmtBF16, true>), unsigned short);
+    else DIVN((k_divide_h16<FmtBF16, false>), unsigned short);
+  }
+#undef DIVN
   HIP_TRY(h, hipGetLastError());
   return IPLS_OK;
 }
@@ -2162,21 +2252,30 @@ static int flat_to_device(ipls_dev* h, const void* flat, int64_t n, int kind, co
       *d = (const unsigned long long*)h->d_scratch;
       *be = kind == IPLS_HOST_BE;
       return IPLS_OK;
-    // float vectors (update_gradient / load_model only reach here with them):
-    // *d then points at floats, 4 B per element on the device and over PCIe
+    // trainer-format vectors (update_gradient / load_model only reach here
+    // with them): *d then points at floats, halves or bfloat16s, 4 or 2 B per
+    // element on the device and over PCIe
     case IPLS_DEV_F32:
-      if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "device float vector not 4-byte aligned");
+    case IPLS_DEV_F16:
+    case IPLS_DEV_BF16: {
+      const int esz = fmt_size(kind_fmt(kind));
+      if ((uintptr_t)flat & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "device vector not %d-byte aligned", esz);
       *d = (const unsigned long long*)flat;
       *be = false;
       return IPLS_OK;
+    }
     case IPLS_HOST_F32:
-      if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "host float vector not 4-byte aligned");
-      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+    case IPLS_HOST_F16:
+    case IPLS_HOST_BF16: {
+      const int esz = fmt_size(kind_fmt(kind));
+      if ((uintptr_t)flat & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "host vector not %d-byte aligned", esz);
+      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(n, 1) * esz)) return rc;
       if (n > 0)
-        if (int rc = stage_h2d(h, h->d_scratch, flat, (size_t)n * 4)) return rc;
+        if (int rc = stage_h2d(h, h->d_scratch, flat, (size_t)n * esz)) return rc;
       *d = (const unsigned long long*)h->d_scratch;
       *be = false;
       return IPLS_OK;
+    }
     default:
       return fail(h, IPLS_E_INVAL, "bad flat kind %d", kind);
   }
@@ -2187,7 +2286,7 @@ int dev_other_replica(ipls_dev* h, int p, int32_t aggregator, const void* src, i
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
   if (n < 0 || (n > 0 && !src)) return fail(h, IPLS_E_INVAL, "bad bucket");
-  if (src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32) return fail(h, IPLS_E_INVAL, "bad flat kind %d", src_kind);
+  if (kind_trainer(src_kind)) return fail(h, IPLS_E_INVAL, "bad flat kind %d", src_kind);
   if ((src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE) && ((uintptr_t)src & 7))
     return fail(h, IPLS_E_INVAL, "device bucket not 8-byte aligned");
   HIP_TRY(h, dev_use(h->device));
@@ -2314,17 +2413,23 @@ int dev_load_model(ipls_dev* h, const void* src, int64_t n, int src_kind) {
   HIP_TRY(h, dev_use(h->device));
   const unsigned long long* d;
   bool be;
-  const bool f32 = src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32;
+  const Fmt fmt = kind_fmt(src_kind);
   // only this engine's segment [flat_base, flat_total) of the model
-  if (int rc = flat_to_device(h, (const char*)src + (f32 ? 4 : 8) * h->flat_base, h->flat_total - h->flat_base,
+  if (int rc = flat_to_device(h, (const char*)src + fmt_size(fmt) * h->flat_base, h->flat_total - h->flat_base,
                               src_kind, &d, &be))
     return rc;
   for (int p = 0; p < h->P; ++p) {
     const int64_t L = h->len[p];
     // IPLS.java:1883-1895: values for j < min((i+1)c, M), count slot 0.0
-    if (f32)
+    if (fmt == kFmtF32)
       hipLaunchKernelGGL(k_load_model_f32, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, (const float*)d,
                          h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+    else if (fmt == kFmtF16)
+      hipLaunchKernelGGL(k_load_model_h16<FmtF16>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream,
+                         (const unsigned short*)d, h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+    else if (fmt == kFmtBF16)
+      hipLaunchKernelGGL(k_load_model_h16<FmtBF16>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream,
+                         (const unsigned short*)d, h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
     else if (be)
       hipLaunchKernelGGL(k_load_model<true>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, d,
                          h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
@@ -2362,18 +2467,20 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
   bool be_in;
   // only the partition's own slice is needed on the device
   const int64_t lo = h->flat_off[p];
-  const bool f32 = src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32;
-  if (f32) {
-    // floats: 4 B per element; a host slice is staged into the first L + 1
-    // doubles' worth of scratch (it needs half of that), the output after it
-    if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "float vector not 4-byte aligned");
+  const Fmt fmt = kind_trainer(src_kind) ? kind_fmt(src_kind) : kFmtF64;
+  if (fmt_trainer(fmt)) {
+    // floats, halves or bfloat16s: 4 or 2 B per element; a host slice is
+    // staged into the first L + 1 doubles' worth of scratch (it needs a half
+    // or a quarter of that), the output after it
+    const int esz = fmt_size(fmt);
+    if ((uintptr_t)flat & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "vector not %d-byte aligned", esz);
     if (int rc = ensure_scratch(h, (size_t)(2 * L + 2) * 8)) return rc;
-    if (src_kind == IPLS_HOST_F32) {
+    if (kind_trainer_host(src_kind)) {
       if (ncopy > 0)
-        if (int rc = stage_h2d(h, h->d_scratch, (const char*)flat + lo * 4, (size_t)ncopy * 4)) return rc;
+        if (int rc = stage_h2d(h, h->d_scratch, (const char*)flat + lo * esz, (size_t)ncopy * esz)) return rc;
       d = (const unsigned long long*)h->d_scratch;
     } else {
-      d = (const unsigned long long*)((const float*)flat + lo);
+      d = (const unsigned long long*)((const char*)flat + lo * esz);
     }
     be_in = false;
   } else if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
@@ -2395,7 +2502,7 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
     return fail(h, IPLS_E_INVAL, "bad dst_kind %d", dst_kind);
   unsigned long long* out = host_out ? (unsigned long long*)((char*)h->d_scratch + (size_t)(L + 1) * 8)
                                      : (unsigned long long*)dst;
-  if (host_out && src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE && src_kind != IPLS_HOST_F32)
+  if (host_out && src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE && !kind_trainer_host(src_kind))
     out = (unsigned long long*)h->d_scratch;
   const bool vec = al16(d) && al16(out);
   const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
@@ -2409,9 +2516,17 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
     if (vec) hipLaunchKernelGGL((k_split_f32<BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const float*)d, (int64_t)0, ncopy, L, out); \
     else hipLaunchKernelGGL((k_split_f32<BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const float*)d, (int64_t)0, ncopy, L, out); \
   } while (0)
-  if (f32) { if (be_out) SPLF(true); else SPLF(false); }
+#define SPLH(H, BO)                                                                                              \
+  do {                                                                                                           \
+    if (vec) hipLaunchKernelGGL((k_split_h16<H, BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, (int64_t)0, ncopy, L, out); \
+    else hipLaunchKernelGGL((k_split_h16<H, BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, (int64_t)0, ncopy, L, out); \
+  } while (0)
+  if (fmt == kFmtF32) { if (be_out) SPLF(true); else SPLF(false); }
+  else if (fmt == kFmtF16) { if (be_out) SPLH(FmtF16, true); else SPLH(FmtF16, false); }
+  else if (fmt == kFmtBF16) { if (be_out) SPLH(FmtBF16, true); else SPLH(FmtBF16, false); }
   else if (be_in) { if (be_out) SPL(true, true); else SPL(true, false); }
   else { if (be_out) SPL(false, true); else SPL(false, false); }
+#undef SPLH
 #undef SPLF
 #undef SPL
   HIP_TRY(h, hipGetLastError());
@@ -2438,16 +2553,18 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
   bool be;
   // only this engine's segment of the gradient vector (flat_base on)
   const int64_t seg = std::max<int64_t>(0, std::min(n, h->flat_total) - h->flat_base);
-  const bool f32 = src_kind == IPLS_DEV_F32 || src_kind == IPLS_HOST_F32;
-  if (src_kind == IPLS_HOST_F32) {
-    // as below, 4 B per element: only the owned partitions' floats cross PCIe
-    if ((uintptr_t)flat & 3) return fail(h, IPLS_E_INVAL, "host float vector not 4-byte aligned");
-    if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(seg, 1) * 4)) return rc;
-    const char* base = (const char*)flat + 4 * h->flat_base;
+  const Fmt fmt = kind_trainer(src_kind) ? kind_fmt(src_kind) : kFmtF64;
+  const int64_t esz = fmt_size(fmt);
+  if (kind_trainer_host(src_kind)) {
+    // as below, 4 or 2 B per element: only the owned partitions' values cross PCIe
+    if ((uintptr_t)flat & (uintptr_t)(esz - 1))
+      return fail(h, IPLS_E_INVAL, "host vector not %d-byte aligned", (int)esz);
+    if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(seg, 1) * esz)) return rc;
+    const char* base = (const char*)flat + esz * h->flat_base;
     for (int i = 0; i < n_owned; ++i) {
       const int64_t lo = h->flat_off[owned[i]] - h->flat_base;
       if (nc[owned[i]] > 0)
-        if (int rc = stage_h2d(h, (char*)h->d_scratch + 4 * lo, base + 4 * lo, (size_t)nc[owned[i]] * 4)) return rc;
+        if (int rc = stage_h2d(h, (char*)h->d_scratch + esz * lo, base + esz * lo, (size_t)nc[owned[i]] * esz)) return rc;
     }
     d = (const unsigned long long*)h->d_scratch;
     be = false;
@@ -2464,7 +2581,7 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     }
     d = (const unsigned long long*)h->d_scratch;
     be = src_kind == IPLS_HOST_BE;
-  } else if (int rc = flat_to_device(h, (const char*)flat + (f32 ? 4 : 8) * h->flat_base, seg, src_kind, &d, &be)) {
+  } else if (int rc = flat_to_device(h, (const char*)flat + esz * h->flat_base, seg, src_kind, &d, &be)) {
     return rc;
   }
   for (int i = 0; i < n_owned; ++i) {
@@ -2475,8 +2592,9 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     const int64_t lo = h->flat_off[p] - h->flat_base;
     // the segment's start decides: partitions whose flat offset is odd read
     // their values at 8 mod 16 and keep the element-per-lane shape
-    // (floats: per partition too -- flat + p*chunk floats is only 4-B aligned in general)
-    const bool vec = (f32 ? al16((const float*)d + lo) : al16(d + lo)) && al16(acc);
+    // (trainer formats: per partition too -- flat + p*chunk elements is only
+    // element-aligned in general)
+    const bool vec = al16((const char*)d + esz * lo) && al16(acc);
     const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
     // Logically-zero accumulator: MODE 2 writes +0.0 + v without reading it
     // (the bits of a fold into zeros)
@@ -2490,9 +2608,17 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     if (vec) hipLaunchKernelGGL((k_split_f32<false, M, true>), g, dim3(kBlock), 0, h->stream, (const float*)d, lo, nc[p], L, acc); \
     else hipLaunchKernelGGL((k_split_f32<false, M, false>), g, dim3(kBlock), 0, h->stream, (const float*)d, lo, nc[p], L, acc); \
   } while (0)
-    if (f32) { if (zero) UPDF(2); else UPDF(1); }
+#define UPDH(H, M)                                                                                              \
+  do {                                                                                                          \
+    if (vec) hipLaunchKernelGGL((k_split_h16<H, false, M, true>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, lo, nc[p], L, acc); \
+    else hipLaunchKernelGGL((k_split_h16<H, false, M, false>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, lo, nc[p], L, acc); \
+  } while (0)
+    if (fmt == kFmtF32) { if (zero) UPDF(2); else UPDF(1); }
+    else if (fmt == kFmtF16) { if (zero) UPDH(FmtF16, 2); else UPDH(FmtF16, 1); }
+    else if (fmt == kFmtBF16) { if (zero) UPDH(FmtBF16, 2); else UPDH(FmtBF16, 1); }
     else if (be) { if (zero) UPD(true, 2); else UPD(true, 1); }
     else { if (zero) UPD(false, 2); else UPD(false, 1); }
+#undef UPDH
 #undef UPDF
 #undef UPD
     HIP_TRY(h, hipGetLastError());
@@ -2508,21 +2634,23 @@ int dev_get_partitions(ipls_dev* h, void* out, int64_t n, int out_kind) {
   const int64_t M = h->flat_total - h->flat_base;
   if (n < M) return fail(h, IPLS_E_RANGE, "output of %lld < model size %lld", (long long)n, (long long)M);
   if (out_kind != IPLS_HOST_F64 && out_kind != IPLS_HOST_BE_CANON && out_kind != IPLS_DEV_F64 &&
-      out_kind != IPLS_DEV_F32 && out_kind != IPLS_HOST_F32)
+      !kind_trainer(out_kind))
     return fail(h, IPLS_E_INVAL, "bad out_kind %d", out_kind);
   HIP_TRY(h, dev_use(h->device));
-  if (out_kind == IPLS_DEV_F32 || out_kind == IPLS_HOST_F32) {
-    // Model.java:388-390: the model narrowed to float, on the device; a host
-    // output comes back as 4 B per value
-    if ((uintptr_t)out & 3) return fail(h, IPLS_E_INVAL, "float output not 4-byte aligned");
-    float* d_f = (float*)out;
-    if (out_kind == IPLS_HOST_F32) {
-      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(M, 1) * 4)) return rc;
-      d_f = (float*)h->d_scratch;
+  if (kind_trainer(out_kind)) {
+    // Model.java:388-390: the model narrowed to float, half or bfloat16, on the
+    // device; a host output comes back as 4 or 2 B per value
+    const Fmt fmt = kind_fmt(out_kind);
+    const int esz = fmt_size(fmt);
+    if ((uintptr_t)out & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "output not %d-byte aligned", esz);
+    void* d_n = out;
+    if (kind_trainer_host(out_kind)) {
+      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(M, 1) * esz)) return rc;
+      d_n = h->d_scratch;
     }
-    if (int rc = divide_range_f32(h, 0, h->P, d_f)) return rc;
-    if (out_kind == IPLS_DEV_F32) return IPLS_OK;
-    return d2h(h, out, d_f, (size_t)M * 4);
+    if (int rc = divide_range_narrow(h, 0, h->P, d_n, fmt)) return rc;
+    if (kind_trainer_dev(out_kind)) return IPLS_OK;
+    return d2h(h, out, d_n, (size_t)M * esz);
   }
   unsigned long long* d_out;
   if (out_kind == IPLS_DEV_F64) {
@@ -2657,15 +2785,15 @@ int dev_reduce_batch_out(ipls_dev* h, int p_first, int n_parts, const void* cons
   IPLS_LOCK(h);
   if (n_parts <= 0 || p_first < 0 || p_first + n_parts > h->P)
     return fail(h, IPLS_E_RANGE, "partitions [%d,%d) out of range [0,%d)", p_first, p_first + n_parts, h->P);
-  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && src_kind != IPLS_DEV_F32)
-    return fail(h, IPLS_E_INVAL, "reduce_batch_out takes device buckets (DEV_F64/DEV_BE/DEV_F32)");
+  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && !kind_trainer_dev(src_kind))
+    return fail(h, IPLS_E_INVAL, "reduce_batch_out takes device buckets (DEV_F64/DEV_BE/DEV_F32/DEV_F16/DEV_BF16)");
   if (dst_kind != IPLS_DEV_F64 && dst_kind != IPLS_DEV_BE)
     return fail(h, IPLS_E_INVAL, "reduce_batch_out writes device buffers (DEV_F64/DEV_BE)");
   if (start_mode < IPLS_START_ACCUM || start_mode > IPLS_START_FIRST) return fail(h, IPLS_E_INVAL, "bad start mode");
   if (!dst || k < 0 || (k > 0 && !bufs)) return fail(h, IPLS_E_INVAL, "bad bucket/destination list");
   HIP_TRY(h, dev_use(h->device));
-  return reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, start_mode, IPLS_TGT_AGG, dst,
-                    dst_kind == IPLS_DEV_BE, nullptr, false, nullptr, src_kind == IPLS_DEV_F32);
+  return reduce_dev(h, p_first, n_parts, bufs, k, kind_fmt(src_kind), start_mode, IPLS_TGT_AGG, dst,
+                    dst_kind == IPLS_DEV_BE);
 }
 
 int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, int k, int src_kind,
@@ -2674,26 +2802,31 @@ int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const
   IPLS_LOCK(h);
   if (n_parts <= 0 || p_first < 0 || p_first + n_parts > h->P)
     return fail(h, IPLS_E_RANGE, "partitions [%d,%d) out of range [0,%d)", p_first, p_first + n_parts, h->P);
-  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && src_kind != IPLS_DEV_F32)
-    return fail(h, IPLS_E_INVAL, "aggregate_round takes device buckets (DEV_F64/DEV_BE/DEV_F32)");
-  const bool f32_in = src_kind == IPLS_DEV_F32;
-  const bool f32_avg = avg_out && (avg_kind == IPLS_DEV_F32 || avg_kind == IPLS_HOST_F32);
-  if (avg_out && !f32_avg && avg_kind != IPLS_DEV_F64 && avg_kind != IPLS_HOST_F64)
-    return fail(h, IPLS_E_INVAL, "avg_kind must be DEV_F64, HOST_F64, DEV_F32 or HOST_F32");
-  if (f32_in)
-    for (int64_t i = 0; i < (int64_t)n_parts * k; ++i)   // before anything is consumed
-      if (!bufs[i] || ((uintptr_t)bufs[i] & 3)) return fail(h, IPLS_E_INVAL, "bucket %lld NULL or not 4-byte aligned", (long long)i);
+  if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE && !kind_trainer_dev(src_kind))
+    return fail(h, IPLS_E_INVAL, "aggregate_round takes device buckets (DEV_F64/DEV_BE/DEV_F32/DEV_F16/DEV_BF16)");
+  const Fmt fmt_in = kind_fmt(src_kind);
+  const bool tr_in = fmt_trainer(fmt_in);
+  // averages narrowed to a trainer format (floats, halves, bfloat16s)
+  const bool tr_avg = avg_out && kind_trainer(avg_kind);
+  const Fmt fmt_avg = tr_avg ? kind_fmt(avg_kind) : kFmtF64;
+  if (avg_out && !tr_avg && avg_kind != IPLS_DEV_F64 && avg_kind != IPLS_HOST_F64)
+    return fail(h, IPLS_E_INVAL, "avg_kind must be DEV_F64, HOST_F64 or a DEV/HOST F32, F16 or BF16 kind");
   if (k < 0 || (k > 0 && !bufs)) return fail(h, IPLS_E_INVAL, "bad bucket list");
+  if (tr_in)
+    for (int64_t i = 0; i < (int64_t)n_parts * k; ++i)   // before anything is consumed
+      if (!bufs[i] || ((uintptr_t)bufs[i] & (uintptr_t)(fmt_size(fmt_in) - 1)))
+        return fail(h, IPLS_E_INVAL, "bucket %lld NULL or not %d-byte aligned", (long long)i, fmt_size(fmt_in));
   HIP_TRY(h, dev_use(h->device));
   const int p_last = p_first + n_parts - 1;
   const int64_t n_avg = h->flat_off[p_last] + h->len[p_last] - 1 - h->flat_off[p_first];
   unsigned long long* d_avg = nullptr;
-  if (f32_avg && n_avg > 0) {
-    if ((uintptr_t)avg_out & 3) return fail(h, IPLS_E_INVAL, "float output not 4-byte aligned");
-    if (avg_kind == IPLS_DEV_F32) {
+  if (tr_avg && n_avg > 0) {
+    if ((uintptr_t)avg_out & (uintptr_t)(fmt_size(fmt_avg) - 1))
+      return fail(h, IPLS_E_INVAL, "output not %d-byte aligned", fmt_size(fmt_avg));
+    if (kind_trainer_dev(avg_kind)) {
       d_avg = (unsigned long long*)avg_out;
     } else {
-      if (int rc = ensure_scratch(h, (size_t)n_avg * 4)) return rc;
+      if (int rc = ensure_scratch(h, (size_t)n_avg * fmt_size(fmt_avg))) return rc;
       d_avg = (unsigned long long*)h->d_scratch;
     }
   } else if (avg_out && n_avg > 0) {
@@ -2707,28 +2840,26 @@ int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const
   }
   bool aligned16 = true;
   for (int64_t i = 0; i < (int64_t)n_parts * k; ++i) aligned16 = aligned16 && !((uintptr_t)bufs[i] & 15);
-  if (aligned16 && !f32_in && !f32_avg) {
+  if (aligned16 && !tr_in && !tr_avg) {
     FinOut fo{d_avg};
-    if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, IPLS_START_ACCUM, IPLS_TGT_AGG,
+    if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, fmt_in, IPLS_START_ACCUM, IPLS_TGT_AGG,
                             nullptr, false, &fo))
       return rc;
   } else {
     // 8-B aligned buckets (frames at odd offsets): the same three steps unfused
-    // float buckets or float averages: the f32 fold / the f32-out divide take
-    // the place of the fused kernel's halves (bit-identical by definition)
-    if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, src_kind == IPLS_DEV_BE, IPLS_START_ACCUM, IPLS_TGT_AGG,
-                            nullptr, false, nullptr, false, nullptr, f32_in))
-      return rc;
+    // trainer-format buckets or averages: the widening fold / the narrowing
+    // divide take the place of the fused kernel's halves (bit-identical by definition)
+    if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, fmt_in, IPLS_START_ACCUM, IPLS_TGT_AGG)) return rc;
     if (int rc = finalize_range(h, p_first, n_parts)) return rc;
     if (d_avg) {
-      if (f32_avg) {
-        if (int rc = divide_range_f32(h, p_first, n_parts, (float*)d_avg)) return rc;
+      if (tr_avg) {
+        if (int rc = divide_range_narrow(h, p_first, n_parts, d_avg, fmt_avg)) return rc;
       } else if (int rc = divide_range(h, p_first, n_parts, d_avg, false)) {
         return rc;
       }
     }
   }
-  if (d_avg && avg_kind == IPLS_HOST_F32) return d2h(h, avg_out, d_avg, (size_t)n_avg * 4);
+  if (d_avg && kind_trainer_host(avg_kind)) return d2h(h, avg_out, d_avg, (size_t)n_avg * fmt_size(fmt_avg));
   if (d_avg && avg_kind == IPLS_HOST_F64) return d2h(h, avg_out, d_avg, (size_t)n_avg * 8);
   return IPLS_OK;
 }
@@ -2874,7 +3005,7 @@ int dev_ingest_pubsub(ipls_dev* h, int target, const uint8_t* const* msgs, const
     int folded = 0;
     for (int p = 0; p < h->P; ++p) {
       if (per_part[p].empty()) continue;
-      if (int rc = reduce_dev(h, p, 1, per_part[p].data(), (int)per_part[p].size(), true, IPLS_START_ACCUM, target))
+      if (int rc = reduce_dev(h, p, 1, per_part[p].data(), (int)per_part[p].size(), kFmtBE, IPLS_START_ACCUM, target))
         return rc;
       folded += (int)per_part[p].size();
     }
@@ -3590,7 +3721,7 @@ int dev_reduce_ext(ipls_dev* h, int n, const int64_t* lens, const void* const* b
   if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
   IPLS_LOCK(h);
   HIP_TRY(h, dev_use(h->device));
-  return reduce_dev(h, 0, n, bufs, k, be_in, start_mode, IPLS_TGT_AGG, dst, false, nullptr, false, lens);
+  return reduce_dev(h, 0, n, bufs, k, be_fmt(be_in), start_mode, IPLS_TGT_AGG, dst, false, nullptr, false, lens);
 }
 
 // Collect_Replicas' length rule (IPLS.java:1225) over this engine's stored

@@ -1826,4 +1826,398 @@ __global__ __launch_bounds__(BS) void k_divide_f32(const DivDesc* __restrict__ p
   for (int64_t i = base + threadIdx.x; i < n; i += BS) o[i] = f(w[i]);
 }
 
+// ===========================================================================
+// half-precision trainer boundary: the float32 boundary above for the two
+// 16-bit formats a trainer under autocast (or a DL4J network built with
+// DataType.HALF / BFLOAT16) holds.  One template parameter H names the format.
+// Sources: v = (double)src[i] -- binary16 by f16 -> f32 -> f64 (both steps
+// exact, subnormals kept), bfloat16 by (bits << 16) taken as an f32 -> f64
+// (exact; a bf16 subnormal is an f32 subnormal) -- then every expression is the
+// f64 kernel's.  Outputs: the f64 quotient rounded to float as k_divide_f32
+// does, then that float rounded to the 16-bit format (ties to even, overflow to
+// +-inf, subnormals kept, -0.0 kept, NaN stays NaN): two roundings, what a
+// trainer gets when it narrows the f32 output itself.  No flush-to-zero: both
+// denormal modes stay on, as in the f32 kernels.
+// ===========================================================================
+typedef unsigned u2w __attribute__((ext_vector_type(2)));
+typedef const IPLS_GLOBAL u2w* gcu2w;
+typedef const IPLS_GLOBAL u4w* gcu4w;
+typedef IPLS_GLOBAL u4w* gu4w;
+typedef const IPLS_GLOBAL unsigned short* gcu16;
+typedef IPLS_GLOBAL unsigned short* gu16;
+
+struct FmtF16 {    // IEEE binary16
+  static __device__ __forceinline__ double one(unsigned short b) { return (double)(float)__builtin_bit_cast(_Float16, b); }
+  static __device__ __forceinline__ double lo(unsigned w) { return one((unsigned short)(w & 0xffffu)); }
+  static __device__ __forceinline__ double hi(unsigned w) { return one((unsigned short)(w >> 16)); }
+  // v_cvt_f16_f32.  The caller's (float)d must stay a rounding of its own (v_cvt_f32_f64): the library is built
+  // with -ffp-contract=off -fno-fast-math, under which hipcc keeps both; without them it folds the pair into one
+  // f64 -> f16 sequence, a single rounding (test_get_partitions_h16's 0x3c00 quotient fails then).
+  static __device__ __forceinline__ unsigned narrow(float f) {
+    return __builtin_bit_cast(unsigned short, (_Float16)f);
+  }
+};
+struct FmtBF16 {   // bfloat16: the upper half of an f32
+  static __device__ __forceinline__ double one(unsigned short b) {
+    return (double)__builtin_bit_cast(float, (unsigned)b << 16);
+  }
+  static __device__ __forceinline__ double lo(unsigned w) { return (double)__builtin_bit_cast(float, w << 16); }
+  static __device__ __forceinline__ double hi(unsigned w) { return (double)__builtin_bit_cast(float, w & 0xffff0000u); }
+  static __device__ __forceinline__ unsigned narrow(float f) {   // v_cvt_pk_bf16_f32 on gfx950
+    return __builtin_bit_cast(unsigned short, (__bf16)f);
+  }
+};
+
+__device__ __forceinline__ unsigned short ld2h(const unsigned short* p) { return *(gcu16)p; }
+// E consecutive 16-bit elements as E / 2 words: one 8-B (E = 4) or 16-B (E = 8) non-temporal load
+template <int E>
+struct HWords {
+  unsigned w[E / 2];
+};
+template <int E>
+__device__ __forceinline__ HWords<E> ldvh(const unsigned short* p) {
+  HWords<E> r;
+  if constexpr (E == 8) {
+    const u4w t = __builtin_nontemporal_load((gcu4w)p);
+    r.w[0] = t.x, r.w[1] = t.y, r.w[2] = t.z, r.w[3] = t.w;
+  } else {
+    static_assert(E == 4, "4 or 8 elements per load");
+    const u2w t = __builtin_nontemporal_load((gcu2w)p);
+    r.w[0] = t.x, r.w[1] = t.y;
+  }
+  return r;
+}
+
+// ---------------------------------------------------------------------------
+// k_reduce_h16: the batched fixed-order fold (k_reduce_f32's contract) over
+// 16-bit buckets.  Grid = n_parts * tiles_per_part blocks of BS lanes; a tile
+// is BS * E * R elements.  A lane owns E consecutive elements per vector: one
+// load per peer per vector, E widenings, E chained f64 adds into E
+// accumulators.  The peer axis is walked in order per element.
+//   E   : 4 is what the library instantiates (with XP = 1).  E = 8 and XP = 0
+//         exist for tools/reduce_h16_sweep.hip only: the layout that lost the
+//         sweep and the no-exchange baselines, kept so that the sweep recorded
+//         in DESIGN.md 3.5.1 can be re-run on the same kernel body.
+//         8 = 16-B loads; the lane's 8 sums are 64 B, so the 8 lanes that own
+//         four adjacent 128-B lines transpose their 16-B pairs among
+//         themselves (two butterfly steps, lane ^ 4 then lane ^ 2) and every
+//         store instruction writes whole lines.
+//         4 = 8-B loads with k_reduce_f32's lane ^ 4 swap unchanged.
+//   VEC : every bucket and destination of the launch is 16-B aligned (decided
+//         by the host); full tiles take the vector path, the partial last tile
+//         E*BS-element vector steps and a scalar remainder.  !VEC: everything
+//         element by element (2-B loads, 8 peers in flight).
+//   MAP : 0 partition-major, 3 partial tiles first (map_block).
+//   PF  : 1 = peer j+1's loads are issued before peer j's values are added.
+//   XP  : 0 = no exchange between lanes, every lane stores its own sums as
+//         they lie (quarter or half lines per store instruction): the sweep's
+//         baseline for the two layouts, not used by the library.
+// ACCUM reads the target in BE_OUT's byte order, like k_reduce.
+// ---------------------------------------------------------------------------
+template <class H, bool BE_OUT, int START, int R, int BS, int MAP, bool VEC, int PF = 0, int E = 8, int XP = 1>
+__global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* __restrict__ bufs,
+                                                   const PartDesc* __restrict__ parts, int k, int tiles_per_part,
+                                                   int n_parts) {
+  constexpr int64_t kTile = (int64_t)BS * E * R;
+  constexpr int kPB = 8;           // peers in flight on the element-by-element path
+  constexpr int kPBV = 32 / E;     // ... and on the partial tile's vector steps: 64 B per lane in flight
+                                   // (8 peers of 16 B next to 8 f64 accumulators spill at 1024 lanes)
+  int q, t;
+  map_block(MAP, gridDim.x, tiles_per_part, n_parts, q, t);
+  if (q >= n_parts) return;
+  const int64_t L = parts[q].len;
+  const int64_t base = (int64_t)t * kTile;
+  if (base >= L) return;
+  unsigned long long* __restrict__ dst = parts[q].dst;
+  const unsigned short* const* __restrict__ pb = bufs + (size_t)q * k;
+  const int tid = threadIdx.x;
+  const int j0 = (START == kFirst) ? 1 : 0;
+
+  auto add = [](double (&a)[E], const HWords<E>& v) {
+#pragma unroll
+    for (int c = 0; c < E / 2; ++c) {
+      a[2 * c] = a[2 * c] + H::lo(v.w[c]);
+      a[2 * c + 1] = a[2 * c + 1] + H::hi(v.w[c]);
+    }
+  };
+  auto init = [&](double (&a)[E], int64_t o) {
+    if constexpr (START == kZero) {
+#pragma unroll
+      for (int c = 0; c < E; ++c) a[c] = 0.0;
+    } else if constexpr (START == kFirst) {
+      const HWords<E> x = ldvh<E>(pb[0] + o);
+#pragma unroll
+      for (int c = 0; c < E / 2; ++c) a[2 * c] = H::lo(x.w[c]), a[2 * c + 1] = H::hi(x.w[c]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < E / 2; ++c) {
+        const d2 x = decode2<BE_OUT>(ld16<false>(dst + o + 2 * c));
+        a[2 * c] = x.x, a[2 * c + 1] = x.y;
+      }
+    }
+  };
+
+  if (VEC && base + kTile <= L) {
+    // lane's first element of the tile; vector r is r * BS * E elements on
+    const int64_t o0 = base + E * (int64_t)tid;
+    double acc[R][E];
+#pragma unroll
+    for (int r = 0; r < R; ++r) init(acc[r], o0 + (int64_t)r * BS * E);
+    if constexpr (PF) {
+      HWords<E> v[R];
+      if (j0 < k) {
+        const unsigned short* __restrict__ src = pb[j0] + o0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = ldvh<E>(src + (int64_t)r * BS * E);
+      }
+      for (int j = j0; j < k; ++j) {
+        HWords<E> nx[R];
+        if (j + 1 < k) {
+          const unsigned short* __restrict__ src = pb[j + 1] + o0;
+#pragma unroll
+          for (int r = 0; r < R; ++r) nx[r] = ldvh<E>(src + (int64_t)r * BS * E);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) add(acc[r], v[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = nx[r];
+      }
+    } else {
+      for (int j = j0; j < k; ++j) {
+        const unsigned short* __restrict__ src = pb[j] + o0;
+        HWords<E> v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = ldvh<E>(src + (int64_t)r * BS * E);
+#pragma unroll
+        for (int r = 0; r < R; ++r) add(acc[r], v[r]);
+      }
+    }
+    if constexpr (!XP) {
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int c = 0; c < E / 2; ++c)
+          __builtin_nontemporal_store(encode2<BE_OUT>(d2{acc[r][2 * c], acc[r][2 * c + 1]}),
+                                      (gu2)(dst + o0 + (int64_t)r * BS * E + 2 * c));
+    } else if constexpr (E == 4) {
+      // k_reduce_f32's store: the 8 lanes that own two adjacent lines swap their
+      // upper pair of sums with lane ^ 4, so each store instruction writes whole lines
+      const bool hi = tid & 4;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int64_t o = o0 + (int64_t)r * BS * 4;
+        const d2 own = d2{acc[r][0], acc[r][1]};
+        const d2 got = d2{__shfl_xor(acc[r][2], 4), __shfl_xor(acc[r][3], 4)};
+        __builtin_nontemporal_store(encode2<BE_OUT>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
+        __builtin_nontemporal_store(encode2<BE_OUT>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
+      }
+    } else {
+      // A lane's 8 sums are 64 B = pairs 0..3; lanes 8g..8g+7 own four adjacent
+      // lines (32 pairs).  Pair i of lane (a2 a1 a0) sits at pair address
+      // 4 * lane + i.  Two exchanges move the line number (the lane's upper two
+      // bits) into the pair index: with lane ^ 4 the pairs whose bit 1 differs
+      // from a2, with lane ^ 2 those whose bit 0 differs from a1.  Afterwards
+      // pair slot i of every lane of the group belongs to line i, at 16-B slot
+      // 4 a0 + 2 a2 + a1 of it, and store instruction i writes line i whole.
+      // Values only move between lanes; every sum is unchanged.
+      const bool a2 = tid & 4, a1 = tid & 2;
+      const int64_t slot = 8 * (tid & 1) + 4 * ((tid >> 2) & 1) + 2 * ((tid >> 1) & 1);   // in doubles
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int64_t g = o0 + (int64_t)r * BS * 8 - 8 * (tid & 7);   // the group's first element
+        double p[4][2], s[4][2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) p[i][0] = acc[r][2 * i], p[i][1] = acc[r][2 * i + 1];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)     // step 1: send pairs with bit 1 != a2
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const double got = __shfl_xor(a2 ? p[i][c] : p[2 + i][c], 4);
+            s[i][c] = a2 ? got : p[i][c];
+            s[2 + i][c] = a2 ? p[2 + i][c] : got;
+          }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)     // step 2: send pairs with bit 0 != a1
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const double got = __shfl_xor(a1 ? s[2 * i][c] : s[2 * i + 1][c], 2);
+            p[2 * i][c] = a1 ? got : s[2 * i][c];
+            p[2 * i + 1][c] = a1 ? s[2 * i + 1][c] : got;
+          }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          __builtin_nontemporal_store(encode2<BE_OUT>(d2{p[i][0], p[i][1]}), (gu2)(dst + g + 16 * i + slot));
+      }
+    }
+    return;
+  }
+  // ------- partial last tile, or a launch with a misaligned operand -------
+  const int64_t end = base + kTile < L ? base + kTile : L;
+  int64_t sb = base;
+  if constexpr (VEC) {
+    for (; sb + E * BS <= end; sb += E * BS) {
+      const int64_t o = sb + E * (int64_t)tid;
+      double a[E];
+      init(a, o);
+      int jj = j0;
+      for (; jj + kPBV <= k; jj += kPBV) {
+        HWords<E> v[kPBV];
+#pragma unroll
+        for (int g = 0; g < kPBV; ++g) v[g] = ldvh<E>(pb[jj + g] + o);
+#pragma unroll
+        for (int g = 0; g < kPBV; ++g) add(a, v[g]);
+      }
+      for (; jj < k; ++jj) add(a, ldvh<E>(pb[jj] + o));
+#pragma unroll
+      for (int c = 0; c < E / 2; ++c)
+        __builtin_nontemporal_store(encode2<BE_OUT>(d2{a[2 * c], a[2 * c + 1]}), (gu2)(dst + o + 2 * c));
+    }
+  }
+  for (int64_t e = sb + tid; e < end; e += BS) {
+    double acc;
+    if constexpr (START == kZero) acc = 0.0;
+    else if constexpr (START == kFirst) acc = H::one(ld2h(pb[0] + e));
+    else acc = decode1<BE_OUT>(ld8(dst + e));
+    int jj = j0;
+    for (; jj + kPB <= k; jj += kPB) {
+      unsigned short v[kPB];
+#pragma unroll
+      for (int g = 0; g < kPB; ++g) v[g] = ld2h(pb[jj + g] + e);
+#pragma unroll
+      for (int g = 0; g < kPB; ++g) acc = acc + H::one(v[g]);
+    }
+    for (; jj < k; ++jj) acc = acc + H::one(ld2h(pb[jj] + e));
+    st8(dst + e, BE_OUT ? f64_to_be(acc) : __builtin_bit_cast(unsigned long long, acc));
+  }
+}
+
+// Shape of the 16-bit-source elementwise kernels when the partition's slice of
+// the flat vector and its destination are both 16-B aligned (VEC, decided by
+// the host per partition: flat + p*chunk is only 2-B aligned in general): a
+// block owns kEwTile consecutive elements, a lane one vector of 8.
+static_assert((int64_t)kBlock * 8 == kEwTile, "one elementwise tile size");
+
+// k_split over a 16-bit flat vector: OrganizeGradients (MODE 0) and
+// UpdateGradient's own accumulate (MODE 1, 2), the expressions of k_split on
+// v = (double)flat[lo + i].  The tile that holds the count slot goes element
+// by element.
+template <class H, bool BE_OUT, int MODE, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_split_h16(const unsigned short* __restrict__ flat, int64_t lo,
+                                                      int64_t ncopy, int64_t L, unsigned long long* __restrict__ dst) {
+  static_assert(MODE == 0 || !BE_OUT, "the folds write native doubles");
+  auto one = [&](int64_t i) {
+    double v;
+    if (i < ncopy) v = H::one(ld2h(flat + lo + i));
+    else if (i == ncopy) v = 1.0;
+    else v = 0.0;
+    if constexpr (MODE == 1) {
+      const double a = __builtin_bit_cast(double, dst[i]);
+      dst[i] = __builtin_bit_cast(unsigned long long, a + v);
+    } else if constexpr (MODE == 2) {
+      dst[i] = __builtin_bit_cast(unsigned long long, 0.0 + v);
+    } else {
+      dst[i] = BE_OUT ? f64_to_be(v) : __builtin_bit_cast(unsigned long long, v);
+    }
+  };
+  if constexpr (VEC) {
+    const int64_t base = (int64_t)blockIdx.x * kEwTile;
+    if (base + kEwTile <= ncopy) {
+      const int64_t i = base + 8 * (int64_t)threadIdx.x;
+      const HWords<8> sv = ldvh<8>(flat + lo + i);
+      u2 dv[4];
+      if constexpr (MODE == 1) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dv[c] = *(gcu2)(dst + i + 2 * c);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const d2 x = d2{H::lo(sv.w[c]), H::hi(sv.w[c])};
+        d2 o;
+        if constexpr (MODE == 1) {
+          const d2 a = __builtin_bit_cast(d2, dv[c]);
+          o = d2{a.x + x.x, a.y + x.y};
+        } else if constexpr (MODE == 2) {
+          o = d2{0.0 + x.x, 0.0 + x.y};
+        } else {
+          o = x;
+        }
+        *(gu2)(dst + i + 2 * c) = encode2<BE_OUT>(o);
+      }
+      return;
+    }
+    const int64_t end = base + kEwTile < L ? base + kEwTile : L;
+    for (int64_t i = base + threadIdx.x; i < end; i += kBlock) one(i);
+  } else {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < L) one(i);
+  }
+}
+
+// k_load_model over a 16-bit model (InitializeWeights from model.params()).
+template <class H>
+__global__ __launch_bounds__(kBlock) void k_load_model_h16(const unsigned short* __restrict__ flat, int64_t lo,
+                                                           int64_t ncopy, int64_t L, double* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= L) return;
+  dst[i] = (i < ncopy) ? H::one(ld2h(flat + lo + i)) : 0.0;
+}
+
+// ---------------------------------------------------------------------------
+// k_divide_h16: the GetPartitions divide narrowed to a 16-bit format:
+//   out[m] = narrow16((float)(cnt == 0.0 ? W[p][j] : W[p][j] / den))
+// k_divide's IEEE double division, rounded to float as k_divide_f32 does, then
+// that float rounded to the format (the two-step rule above).  Never a 16-bit
+// or f32 division, never a reciprocal.  Tiles are laid over the OUTPUT as in
+// k_divide_f32: block 0 writes the `head` values up to the first 128-B line of
+// this partition's output, then every lane stores 16 B = 8 values and a wave
+// whole lines; W is read with 8-B loads.
+// ---------------------------------------------------------------------------
+constexpr int kDivV16 = 1;
+constexpr int64_t kDivTile16 = (int64_t)kBlock * 8 * kDivV16;
+
+template <class H, bool SECURE, int BS = kBlock, int V = kDivV16>
+__global__ __launch_bounds__(BS) void k_divide_h16(const DivDesc* __restrict__ parts, const double* __restrict__ arena,
+                                                   unsigned short* __restrict__ out, int tiles_per_part) {
+  constexpr int64_t kTile = (int64_t)BS * 8 * V;
+  static_assert(BS % 64 == 0, "whole waves");
+  const int q = blockIdx.x / tiles_per_part;
+  const int t = blockIdx.x - q * tiles_per_part;
+  const DivDesc d = parts[q];
+  const int64_t n = d.len - 1;
+  const double* w = arena + d.w_off;
+  const double cnt = w[d.len - 1];
+  const double den = SECURE ? 1e12 * cnt : cnt;   // IPLS.java:1167
+  auto f = [&](double x) -> unsigned { return H::narrow((float)((cnt == 0.0) ? x : x / den)); };
+  unsigned short* o = out + d.out_off;
+  const int64_t to_line = (64 - (int64_t)(((uintptr_t)o >> 1) & 63)) & 63;   // values to a 128-B boundary
+  const int64_t head = to_line < n ? to_line : n;
+  if (t == 0 && threadIdx.x < head) *(gu16)(o + threadIdx.x) = (unsigned short)f(w[threadIdx.x]);
+  const int64_t base = (int64_t)t * kTile + head;
+  if (base >= n) return;
+  if (base + kTile <= n) {
+    // wave (threadIdx.x / 64) owns [base + wave * 512 * V, + 512 * V)
+    const int64_t wave_base = base + (int64_t)(threadIdx.x >> 6) * 512 * V + 8 * (threadIdx.x & 63);
+    double x[V][8];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int64_t i = wave_base + (int64_t)v * 512;
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        x[v][c] = __builtin_nontemporal_load((const __attribute__((address_space(1))) double*)(w + i + c));
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int64_t i = wave_base + (int64_t)v * 512;
+      u4w y;
+      y.x = f(x[v][0]) | (f(x[v][1]) << 16);
+      y.y = f(x[v][2]) | (f(x[v][3]) << 16);
+      y.z = f(x[v][4]) | (f(x[v][5]) << 16);
+      y.w = f(x[v][6]) | (f(x[v][7]) << 16);
+      __builtin_nontemporal_store(y, (gu4w)(o + i));
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < n; i += BS) *(gu16)(o + i) = (unsigned short)f(w[i]);
+}
+
 }  // namespace ipls

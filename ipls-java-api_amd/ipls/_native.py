@@ -25,9 +25,11 @@ HOST_F64, HOST_BE, HOST_FRAME, DEV_F64, DEV_BE, HOST_BE_CANON, HOST_PAIR = 0, 1,
 HOST_TEXT, DEV_TEXT = 7, 8
 HOST_DARR, HOST_DLIST = 9, 10
 DEV_F32, HOST_F32 = 11, 12        # the float32 trainer boundary (include/ipls_agg.h)
+DEV_F16, HOST_F16, DEV_BF16, HOST_BF16 = 13, 14, 15, 16   # the half-precision one: IEEE binary16, bfloat16
 SAVED_SET, SAVED_BLEND = 0, 1
 KERNEL_REDUCE, KERNEL_ROUND, KERNEL_FOLD1, KERNEL_REDUCE_SCALAR = 1, 2, 3, 4
 KERNEL_REDUCE_F32 = 5
+KERNEL_REDUCE_H16 = 6
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2

@@ -42,10 +42,11 @@ from . import _native as N
 class DeviceBuffer:
     """A device-resident operand: address, element count, big-endian or not.
 
-    ``dtype`` is ``"f64"`` (doubles, or big-endian double bytes) or ``"f32"``
+    ``dtype`` is ``"f64"`` (doubles, or big-endian double bytes), ``"f32"``
     (a trainer's float parameters or gradients, Model.java:423 / 388-390: the
-    library widens or narrows them on the device); ``n`` counts elements of
-    that dtype.
+    library widens or narrows them on the device), ``"half"`` (IEEE binary16)
+    or ``"bf16"`` (bfloat16) -- what a trainer under autocast holds; ``n``
+    counts elements of that dtype.  Only f64 buffers can be big-endian.
 
     The handle's HIP stream is non-blocking (include/ipls_agg.h): bytes
     written by torch or the null stream must be complete before the call
@@ -57,32 +58,58 @@ class DeviceBuffer:
     dtype: str = "f64"
 
     def __post_init__(self):
-        if self.dtype not in ("f64", "f32"):
-            raise ValueError(f"dtype must be 'f64' or 'f32', not {self.dtype!r}")
-        if self.dtype == "f32" and self.big_endian:
-            raise ValueError("big-endian buffers hold doubles: dtype='f32' cannot be big_endian")
+        if self.dtype not in ("f64", "f32", "half", "bf16"):
+            raise ValueError(f"dtype must be 'f64', 'f32', 'half' or 'bf16', not {self.dtype!r}")
+        if self.dtype != "f64" and self.big_endian:
+            raise ValueError(f"big-endian buffers hold doubles: dtype={self.dtype!r} cannot be big_endian")
 
     @classmethod
     def from_tensor(cls, t, big_endian: bool = False) -> "DeviceBuffer":
-        """A ``torch.float32`` tensor gives an f32 buffer of ``numel()``
-        elements; every other dtype is a carrier of 8-byte values (float64,
-        or uint8 / int64 holding doubles or big-endian double bytes)."""
+        """A ``torch.float32`` tensor gives an f32 buffer, a ``torch.float16``
+        one a ``"half"`` buffer and a ``torch.bfloat16`` one a ``"bf16"``
+        buffer, each of ``numel()`` elements; every other dtype is a carrier
+        of 8-byte values (float64, or uint8 / int64 holding doubles or
+        big-endian double bytes).  The two 16-bit dtypes used to be read as
+        such carriers (``numel() * 2 // 8`` "doubles"), which could only ever
+        produce garbage; they are now the values they hold."""
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError("need a contiguous device tensor")
-        if str(t.dtype) == "torch.float32":
-            return cls(int(t.data_ptr()), t.numel(), big_endian, "f32")
+        trainer = _TORCH_DTYPES.get(str(t.dtype))
+        if trainer is not None:
+            return cls(int(t.data_ptr()), t.numel(), big_endian, trainer)
         return cls(int(t.data_ptr()), t.numel() * t.element_size() // 8, big_endian)
 
     @property
     def kind(self) -> int:
-        if self.dtype == "f32":
-            return N.DEV_F32
+        if self.dtype != "f64":
+            return _DEV_KIND[self.dtype]
         return N.DEV_BE if self.big_endian else N.DEV_F64
+
+
+# the trainer dtypes (widened / narrowed on the device): torch dtype -> name,
+# name -> DEV kind, HOST kind, element noun of the error messages
+_TORCH_DTYPES = {"torch.float32": "f32", "torch.float16": "half", "torch.bfloat16": "bf16"}
+_DEV_KIND = {"f32": N.DEV_F32, "half": N.DEV_F16, "bf16": N.DEV_BF16}
+_HOST_KIND = {"f32": N.HOST_F32, "half": N.HOST_F16, "bf16": N.HOST_BF16}
+_NOUN = {"f64": "doubles", "f32": "floats", "half": "halves", "bf16": "bfloat16s"}
+
+
+def _out_dtype(dtype):
+    """'f64', 'f32', 'half' or 'bf16' for the ``dtype=`` of GetPartitions /
+    aggregate_round: a numpy dtype, or the string "bf16" (numpy has no
+    bfloat16: the host array then holds the bit patterns as uint16)."""
+    if isinstance(dtype, str) and dtype == "bf16":
+        return "bf16"
+    d = np.dtype(dtype)
+    return "f32" if d == np.float32 else "half" if d == np.float16 else "f64"
+
+
+_NP_OUT = {"f64": np.float64, "f32": np.float32, "half": np.float16, "bf16": np.uint16}
 
 
 def _bucket_table(buckets, lengths, p_first: int):
     """(flat pointer list, k) of a batched call's bucket table, with the checks
-    of _bucket_table_kind (lengths in elements, no mixing of f32 and f64)."""
+    of _bucket_table_kind (lengths in elements, one dtype per table)."""
     return _bucket_table_kind(buckets, lengths, p_first)[:2]
 
 
@@ -92,9 +119,10 @@ def _bucket_table_kind(buckets, lengths, p_first: int, big_endian: bool = False)
     C-ABI takes bare pointers and reads L_p elements from each
     (include/ipls_agg.h), so a DeviceBuffer shorter than its partition -- in
     elements of its dtype -- is refused here, before any launch could read
-    past it.  The kind is DEV_F32 when the DeviceBuffers are f32 (one call
-    folds one kind: a table that mixes f32 and f64 buffers is refused), else
-    DEV_BE / DEV_F64 by ``big_endian``, which applies to f64 buckets only.
+    past it.  The kind is DEV_F32 / DEV_F16 / DEV_BF16 when the DeviceBuffers
+    are f32 / half / bf16 (one call folds one kind: a table that mixes dtypes
+    is refused), else DEV_BE / DEV_F64 by ``big_endian``, which applies to f64
+    buckets only.
     Raw integer addresses are the caller's contract; partitions out of range
     are left to the library's range check."""
     n_parts = len(buckets)
@@ -110,24 +138,31 @@ def _bucket_table_kind(buckets, lengths, p_first: int, big_endian: bool = False)
             if isinstance(b, DeviceBuffer):
                 if b.n < need:
                     raise ValueError(f"partition {p} needs buckets of {need} "
-                                     f"{'floats' if b.dtype == 'f32' else 'doubles'}, a DeviceBuffer holds {b.n}")
+                                     f"{_NOUN[b.dtype]}, a DeviceBuffer holds {b.n}")
                 dtypes.add(b.dtype)
                 flat.append(b.ptr)
             else:
                 flat.append(int(b))
     if len(dtypes) > 1:
-        raise ValueError("a bucket table holds f32 or f64 DeviceBuffers, not both")
-    if dtypes == {"f32"}:
+        raise ValueError("a bucket table holds DeviceBuffers of one dtype (f64, f32, half or bf16), not a mix")
+    if dtypes and dtypes != {"f64"}:
         if big_endian:
             raise ValueError("big_endian applies to f64 buckets only")
-        return flat, k, N.DEV_F32
+        return flat, k, _DEV_KIND[dtypes.pop()]
     return flat, k, (N.DEV_BE if big_endian else N.DEV_F64)
 
 
 def _host_operand(x, big_endian: bool, f32: bool = False):
     """(pointer, n_elements, kind, keepalive) for a host operand.  ``f32``: the
-    call takes HOST_F32 (include/ipls_agg.h), so a numpy float32 array goes as
-    it is and is widened on the device; elsewhere it is widened here."""
+    call takes the HOST trainer kinds (include/ipls_agg.h), so a numpy float32
+    or float16 array, or a contiguous CPU torch.float16 / torch.bfloat16
+    tensor, goes as it is (4 or 2 B per element) and is widened on the device;
+    elsewhere it is widened here."""
+    tdt = str(getattr(x, "dtype", "")) if hasattr(x, "data_ptr") else ""
+    if tdt in ("torch.float16", "torch.bfloat16"):   # a CPU tensor (numpy has no bfloat16)
+        if f32 and x.is_contiguous() and x.device.type == "cpu":
+            return int(x.data_ptr()), x.numel(), _HOST_KIND[_TORCH_DTYPES[tdt]], x
+        x = x.double().numpy()
     if isinstance(x, (bytes, bytearray, memoryview)):
         a = np.frombuffer(x, dtype=np.uint8)
     else:
@@ -141,6 +176,9 @@ def _host_operand(x, big_endian: bool, f32: bool = False):
     if f32 and a.dtype == np.float32:   # a trainer's floats: 4 B per element to the device, widened there
         a = np.ascontiguousarray(a)
         return a.ctypes.data, a.size, N.HOST_F32, a
+    if f32 and a.dtype == np.float16:   # halves: 2 B per element to the device, widened there
+        a = np.ascontiguousarray(a)
+        return a.ctypes.data, a.size, N.HOST_F16, a
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a.ctypes.data, a.size, N.HOST_F64, a
 
@@ -567,8 +605,8 @@ class Aggregator:
         flat, k, kind = _bucket_table_kind(buckets, self.lengths, p_first, big_endian_in)
         for q, d in enumerate(dsts):
             p = p_first + q
-            if isinstance(d, DeviceBuffer) and d.dtype == "f32":
-                raise N.IplsError(N.IPLS_E_INVAL, "reduce_batch_out writes doubles or big-endian bytes, not f32")
+            if isinstance(d, DeviceBuffer) and d.dtype != "f64":
+                raise N.IplsError(N.IPLS_E_INVAL, f"reduce_batch_out writes doubles or big-endian bytes, not {d.dtype}")
             if isinstance(d, DeviceBuffer) and 0 <= p < self.n_partitions and d.n < self.lengths[p]:
                 raise ValueError(f"partition {p} needs a destination of {self.lengths[p]} doubles, "
                                  f"the DeviceBuffer holds {d.n}")
@@ -585,9 +623,13 @@ class Aggregator:
         AggregatePartition (IPLS.java:1248-1274) and the GetPartitions divide
         (IPLS.java:1159-1174).  Returns the averaged values of the partitions
         (host array, or ``out`` when a DeviceBuffer is given), or None.
-        f32 buckets are widened in the fold; an f32 ``out`` (or
+        f32, half and bf16 buckets are widened in the fold; an f32 ``out`` (or
         ``dtype=np.float32`` for the host array) gets the averages narrowed
-        once to float, as Model.java:388-390 narrows them."""
+        once to float, as Model.java:388-390 narrows them; a half / bf16
+        ``out`` (or ``dtype=np.float16`` / ``dtype="bf16"``, the latter a
+        uint16 array of bit patterns) gets that float rounded again to the
+        16-bit format (include/ipls_agg.h: two roundings, what narrowing the
+        f32 output gives)."""
         n_parts = len(buckets)
         flat, k, kind = _bucket_table_kind(buckets, self.lengths, p_first, big_endian)
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
@@ -599,12 +641,13 @@ class Aggregator:
                 if out.n < need:
                     raise ValueError(f"the averages of partitions {p_first}..{last} need {need} values, "
                                      f"the DeviceBuffer holds {out.n}")
-            ap, ak, res = out.ptr, (N.DEV_F32 if out.dtype == "f32" else N.DEV_F64), out
+            ap, ak, res = out.ptr, _DEV_KIND.get(out.dtype, N.DEV_F64), out
         elif with_average:
             last = p_first + n_parts - 1
             n = self.offsets[last] + self.lengths[last] - 1 - self.offsets[p_first]
-            res = np.empty(max(0, n), dtype=np.float32 if np.dtype(dtype) == np.float32 else np.float64)
-            ak = N.HOST_F32 if res.dtype == np.float32 else N.HOST_F64
+            od = _out_dtype(dtype)
+            res = np.empty(max(0, n), dtype=_NP_OUT[od])
+            ak = _HOST_KIND.get(od, N.HOST_F64)
             ap = res.ctypes.data if res.size else None
         self._chk(self._lib.ipls_agg_aggregate_round(self._h, p_first, n_parts, arr, k, kind, ap, ak))
         return res
@@ -746,15 +789,19 @@ class Aggregator:
         rate) and a memoryview of those 8*M bytes is returned, ready for
         ``sendall`` without another copy.  An f32 DeviceBuffer ``out``, or
         ``dtype=np.float32`` for the host array, gets every value rounded once
-        to float on the device (Model.java:388-390), 4 bytes per value."""
+        to float on the device (Model.java:388-390), 4 bytes per value.  A
+        half / bf16 DeviceBuffer, ``dtype=np.float16`` (a numpy float16 array)
+        or ``dtype="bf16"`` (a numpy uint16 array of the bfloat16 bit
+        patterns) gets that float rounded again to the 16-bit format, 2 bytes
+        per value."""
         n = self.flat_size
         if isinstance(out, DeviceBuffer):
-            self._chk(self._lib.ipls_agg_get_partitions(self._h, out.ptr, out.n,
-                                                        N.DEV_F32 if out.dtype == "f32" else N.DEV_F64))
+            self._chk(self._lib.ipls_agg_get_partitions(self._h, out.ptr, out.n, _DEV_KIND.get(out.dtype, N.DEV_F64)))
             return out
-        if np.dtype(dtype) == np.float32 and out is None and not wire:
-            buf = np.empty(n, dtype=np.float32)
-            self._chk(self._lib.ipls_agg_get_partitions(self._h, buf.ctypes.data, n, N.HOST_F32))
+        od = _out_dtype(dtype)
+        if od != "f64" and out is None and not wire:
+            buf = np.empty(n, dtype=_NP_OUT[od])
+            self._chk(self._lib.ipls_agg_get_partitions(self._h, buf.ctypes.data, n, _HOST_KIND[od]))
             return buf
         if isinstance(out, PinnedBuffer):
             if out.nbytes < 8 * n:
@@ -815,7 +862,7 @@ class Aggregator:
         of the partition other than its owner, IPLS.java:1402-1431)."""
         n_parts = len(buckets)
         flat, k, bk = _bucket_table_kind(buckets, self.lengths, p_first)
-        if bk == N.DEV_F32:
+        if bk not in (N.DEV_F64, N.DEV_BE):
             raise N.IplsError(N.IPLS_E_INVAL, "reduce_partial takes f64 buckets (DEV_F64/DEV_BE)")
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
         self._chk(self._lib.ipls_agg_reduce_partial(self._h, slot, p_first, n_parts, arr, k,
