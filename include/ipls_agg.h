@@ -683,10 +683,10 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
 #define IPLS_KERNEL_ROUND         2  /* k_round (fused) */
 #define IPLS_KERNEL_FOLD1         3  /* k_fold1         */
 #define IPLS_KERNEL_REDUCE_SCALAR 4  /* k_reduce_scalar */
-#define IPLS_KERNEL_REDUCE_F32    5  /* k_reduce_f32: DEV_F32 buckets; a tile is block x 4 x vectors
+#define IPLS_KERNEL_REDUCE_F32    5  /* k_reduce_narrow over DEV_F32 buckets; a tile is block x 4 x vectors
                                         elements; shape 0; seqf 1 when every operand was 16-B
                                         aligned (vector path), 0 for the element-by-element form */
-#define IPLS_KERNEL_REDUCE_H16    6  /* k_reduce_h16: DEV_F16 / DEV_BF16 buckets; a tile is block x 4 x
+#define IPLS_KERNEL_REDUCE_H16    6  /* k_reduce_narrow over DEV_F16 / DEV_BF16 buckets; a tile is block x 4 x
                                         vectors elements; shape 0; seqf 1 when every operand was 16-B
                                         aligned (vector path), 0 for the element-by-element form */
 #define IPLS_SHAPE_BIG    1

@@ -88,27 +88,6 @@ struct ipls_stage {
   bool free_pending = false;
 };
 
-// Element format of a source or an output: native doubles, big-endian double
-// bytes, or one of the trainer formats of include/ipls_agg.h (floats, IEEE
-// binary16, bfloat16), which the kernels widen / narrow in registers.  The
-// values are also the format codes of the accumulate_async queues.
-enum Fmt : int { kFmtF64 = 0, kFmtBE = 1, kFmtF32 = 2, kFmtF16 = 3, kFmtBF16 = 4 };
-constexpr Fmt be_fmt(bool be) { return be ? kFmtBE : kFmtF64; }
-constexpr bool fmt_trainer(Fmt f) { return f >= kFmtF32; }                    // widened on the device
-constexpr bool fmt_h16(Fmt f) { return f == kFmtF16 || f == kFmtBF16; }
-constexpr int fmt_size(Fmt f) { return f == kFmtF32 ? 4 : fmt_h16(f) ? 2 : 8; }   // bytes per element (= alignment)
-// format of an operand kind where the trainer kinds are accepted; every other kind counts as doubles
-constexpr Fmt kind_fmt(int kind) {
-  return kind == IPLS_DEV_BE || kind == IPLS_HOST_BE                ? kFmtBE
-         : kind == IPLS_DEV_F32 || kind == IPLS_HOST_F32            ? kFmtF32
-         : kind == IPLS_DEV_F16 || kind == IPLS_HOST_F16            ? kFmtF16
-         : kind == IPLS_DEV_BF16 || kind == IPLS_HOST_BF16          ? kFmtBF16
-                                                                    : kFmtF64;
-}
-constexpr bool kind_trainer_dev(int kind) { return kind == IPLS_DEV_F32 || kind == IPLS_DEV_F16 || kind == IPLS_DEV_BF16; }
-constexpr bool kind_trainer_host(int kind) { return kind == IPLS_HOST_F32 || kind == IPLS_HOST_F16 || kind == IPLS_HOST_BF16; }
-constexpr bool kind_trainer(int kind) { return kind_trainer_dev(kind) || kind_trainer_host(kind); }
-
 struct ipls_dev {
   std::mutex mu;
   std::string err;
@@ -854,8 +833,24 @@ void launch_reduce_scalar(bool be_in, bool be_out, int start, dim3 grid, hipStre
 #undef RS
 }
 
-// ---- kernel dispatch: k_reduce_f32 (DEV_F32 buckets) ----
-// One shape for every grid: 1024-lane workgroups, 2 vectors of 4 floats per
+// Calls f with a value of the kernels' format type for a trainer format.
+template <class F>
+auto with_narrow(Fmt fmt, F&& f) {
+  switch (fmt) {
+    case kFmtF32: return f(FmtF32{});
+    case kFmtF16: return f(FmtF16{});
+    case kFmtBF16: return f(FmtBF16{});
+    default: break;
+  }
+  // a caller without its fmt_trainer guard: never run a narrow kernel on doubles
+  fprintf(stderr, "ipls_agg: with_narrow called with format %d\n", (int)fmt);
+  abort();
+}
+
+// ---- kernel dispatch: k_reduce_narrow (DEV_F32 / DEV_F16 / DEV_BF16 buckets) ----
+// One shape per element size (narrow_shape), for every grid; the two blocks
+// below say why floats and 16-bit elements differ in vectors per lane.
+// Floats: 1024-lane workgroups, 2 vectors of 4 floats per
 // lane (32 KiB of a bucket per block, 16 accumulator VGPRs), the next peer's 2
 // loads issued before this peer's values are added (PF = 1; 70 VGPRs, no
 // spills).  Same process, same buckets, single launches
@@ -863,39 +858,10 @@ void launch_reduce_scalar(bool be_in, bool be_out, int start, dim3 grid, hipStre
 // 16 x 4M x 32 at 79.8 % of 8 TB/s against 70.3-77.0 % for the other
 // prefetching shapes of 256..1024 lanes x 2..8 vectors and 70.6-79.8 % without
 // the prefetch; 1 x 4M x 32 at 82.4 %, the best of the sweep; ETHModel's
-// 3 x 147,870 x 3 within 5 % of the best.  Partial last tiles are scheduled
-// first (map 3) as for k_reduce.  vec: every bucket and destination is 16-B
-// aligned; otherwise the same grid runs element by element.
-constexpr int kF32BS = 1024, kF32R = 2, kF32PF = 1;
-ipls_launch_info launch_reduce_f32(bool be_out, int start, bool vec, int64_t maxL, int n_parts, hipStream_t st,
-                                   const float* const* bufs, const PartDesc* parts, int k) {
-  const int64_t tile = (int64_t)kF32BS * 4 * kF32R;
-  const int64_t tpp = (maxL + tile - 1) / tile;
-  const bool partial = tpp > 1 && maxL % tile != 0;
-  const dim3 grid((unsigned)(tpp * n_parts));
-#define RF(BO, ST, MAP, V)                                                                                        \
-  hipLaunchKernelGGL((k_reduce_f32<BO, ST, kF32R, kF32BS, MAP, V, (V ? kF32PF : 0)>), grid, dim3(kF32BS), 0, st, bufs, \
-                     parts, k, (int)tpp, n_parts)
-#define RF3(BO, ST)                                         \
-  do {                                                      \
-    if (!vec) RF(BO, ST, 0, false);                         \
-    else if (partial) RF(BO, ST, 3, true);                  \
-    else RF(BO, ST, 0, true);                               \
-  } while (0)
-#define RF2(BO) do { if (start == kZero) RF3(BO, kZero); else if (start == kFirst) RF3(BO, kFirst); else RF3(BO, kAccum); } while (0)
-  if (be_out) RF2(true);
-  else RF2(false);
-#undef RF2
-#undef RF3
-#undef RF
-  return launch_info(IPLS_KERNEL_REDUCE_F32, 0, kF32BS, kF32R, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false,
-                     be_out, start);
-}
-
-// ---- kernel dispatch: k_reduce_h16 (DEV_F16 / DEV_BF16 buckets) ----
-// One shape for every grid: layout A of the sweep -- 8-B loads, kH16E = 4
-// elements per lane per vector, k_reduce_f32's lane ^ 4 swap before the stores
-// -- on 1024-lane workgroups with 4 vectors per lane (32 KiB of a bucket per
+// 3 x 147,870 x 3 within 5 % of the best.
+// 16-bit formats: layout A of the sweep -- 8-B loads, 4 elements per lane per
+// vector, the same lane ^ 4 swap before the stores as for floats -- on
+// 1024-lane workgroups with 4 vectors per lane (32 KiB of a bucket per
 // block, 32 accumulator VGPRs), the next peer's 4 loads issued before this
 // peer's values are added (68-90 VGPRs over the start modes, no scratch).
 // Same process, same buckets, single launches, sums 128-B aligned as in the
@@ -913,31 +879,39 @@ ipls_launch_info launch_reduce_f32(bool be_out, int start, bool vec, int64_t max
 // Partial last tiles are scheduled first (map 3) as for k_reduce.  vec: every
 // bucket and destination is 16-B aligned; otherwise the same grid runs element
 // by element.
-constexpr int kH16BS = 1024, kH16R = 4, kH16PF = 1, kH16E = 4;
-template <class H>
-ipls_launch_info launch_reduce_h16(bool be_out, int start, bool vec, int64_t maxL, int n_parts, hipStream_t st,
-                                   const unsigned short* const* bufs, const PartDesc* parts, int k) {
-  const int64_t tile = (int64_t)kH16BS * kH16E * kH16R;
+struct NarrowShape {
+  int bs, r, pf, e;   // lanes, vectors per lane, next-peer prefetch, elements per lane per vector
+  int kernel;         // what the launch record names
+};
+template <class S>
+constexpr NarrowShape narrow_shape() {
+  return sizeof(typename S::elem) == 4 ? NarrowShape{1024, 2, 1, 4, IPLS_KERNEL_REDUCE_F32}
+                                       : NarrowShape{1024, 4, 1, 4, IPLS_KERNEL_REDUCE_H16};
+}
+template <class S>
+ipls_launch_info launch_reduce_narrow(bool be_out, int start, bool vec, int64_t maxL, int n_parts, hipStream_t st,
+                                      const typename S::elem* const* bufs, const PartDesc* parts, int k) {
+  constexpr NarrowShape K = narrow_shape<S>();
+  const int64_t tile = (int64_t)K.bs * K.e * K.r;
   const int64_t tpp = (maxL + tile - 1) / tile;
   const bool partial = tpp > 1 && maxL % tile != 0;
   const dim3 grid((unsigned)(tpp * n_parts));
-#define RH(BO, ST, MAP, V)                                                                                       \
-  hipLaunchKernelGGL((k_reduce_h16<H, BO, ST, kH16R, kH16BS, MAP, V, (V ? kH16PF : 0), kH16E>), grid, dim3(kH16BS), \
-                     0, st, bufs, parts, k, (int)tpp, n_parts)
-#define RH3(BO, ST)                                         \
+#define RN(BO, ST, MAP, V)                                                                                       \
+  hipLaunchKernelGGL((k_reduce_narrow<S, BO, ST, K.r, K.bs, MAP, V, (V ? K.pf : 0), K.e>), grid, dim3(K.bs), 0, st, \
+                     bufs, parts, k, (int)tpp, n_parts)
+#define RN3(BO, ST)                                         \
   do {                                                      \
-    if (!vec) RH(BO, ST, 0, false);                         \
-    else if (partial) RH(BO, ST, 3, true);                  \
-    else RH(BO, ST, 0, true);                               \
+    if (!vec) RN(BO, ST, 0, false);                         \
+    else if (partial) RN(BO, ST, 3, true);                  \
+    else RN(BO, ST, 0, true);                               \
   } while (0)
-#define RH2(BO) do { if (start == kZero) RH3(BO, kZero); else if (start == kFirst) RH3(BO, kFirst); else RH3(BO, kAccum); } while (0)
-  if (be_out) RH2(true);
-  else RH2(false);
-#undef RH2
-#undef RH3
-#undef RH
-  return launch_info(IPLS_KERNEL_REDUCE_H16, 0, kH16BS, kH16R, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false,
-                     be_out, start);
+#define RN2(BO) do { if (start == kZero) RN3(BO, kZero); else if (start == kFirst) RN3(BO, kFirst); else RN3(BO, kAccum); } while (0)
+  if (be_out) RN2(true);
+  else RN2(false);
+#undef RN2
+#undef RN3
+#undef RN
+  return launch_info(K.kernel, 0, K.bs, K.r, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false, be_out, start);
 }
 
 // Core of accumulate / reduce_batch: all pointers device-resident.  The
@@ -1060,15 +1034,12 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
     for (int q = p_first; q < p_first + n_parts; ++q) h->agg_zero[q] = h->rep_zero[q] = 1;
     return IPLS_OK;
   }
-  if (fmt_in == kFmtF32) {
-    h->last_launch = launch_reduce_f32(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
-                                       (const float* const*)dbufs, dparts, k);
-  } else if (fmt_in == kFmtF16) {
-    h->last_launch = launch_reduce_h16<FmtF16>(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
-                                               (const unsigned short* const*)dbufs, dparts, k);
-  } else if (fmt_in == kFmtBF16) {
-    h->last_launch = launch_reduce_h16<FmtBF16>(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
-                                                (const unsigned short* const*)dbufs, dparts, k);
+  if (tr_in) {
+    h->last_launch = with_narrow(fmt_in, [&](auto s) {
+      typedef decltype(s) S;
+      return launch_reduce_narrow<S>(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
+                                     (const typename S::elem* const*)dbufs, dparts, k);
+    });
   } else if (aligned16) {
     h->last_launch = launch_reduce(be_in, be_out, start, maxL, n_parts, h->stream, dbufs, dparts, k);
   } else {
@@ -2044,8 +2015,8 @@ static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, 
   return IPLS_OK;
 }
 
-// The same divide narrowed to a trainer format: d_out holds floats
-// (k_divide_f32), halves or bfloat16s (k_divide_h16).
+// The same divide narrowed to a trainer format (k_divide_narrow): d_out holds
+// floats, halves or bfloat16s.
 static int divide_range_narrow(ipls_dev* h, int p0, int np, void* d_out, Fmt fmt) {
   std::vector<DivDesc> dd(np);
   int64_t maxn = 0;
@@ -2057,22 +2028,17 @@ static int divide_range_narrow(ipls_dev* h, int p0, int np, void* d_out, Fmt fmt
   if (maxn <= 0) return IPLS_OK;
   void* dtab = nullptr;
   if (int rc = upload_table(h, dd.data(), dd.size() * sizeof(DivDesc), &dtab)) return rc;
-  const int64_t tile = fmt == kFmtF32 ? kDivTile32 : kDivTile16;
-  const int tpp = (int)((maxn + tile - 1) / tile);
+  const int tpp = (int)((maxn + kDivTile - 1) / kDivTile);
   const dim3 g((unsigned)tpp * np);
-#define DIVN(KERNEL, T)                                                                                          \
-  hipLaunchKernelGGL(KERNEL, g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena, (T*)d_out, tpp)
-  if (fmt == kFmtF32) {
-    if (h->secure) DIVN((k_divide_f32<true>), float);
-    else DIVN((k_divide_f32<false>), float);
-  } else if (fmt == kFmtF16) {
-    if (h->secure) DIVN((k_divide_h16<FmtF16, true>), unsigned short);
-    else DIVN((k_divide_h16<FmtF16, false>), unsigned short);
-  } else {
-    if (h->secure) DIVN((k_divide_h16<FmtBF16, true>), unsigned short);
-    else DIVN((k_divide_h16<FmtBF16, false>), unsigned short);
-  }
+  with_narrow(fmt, [&](auto s) {
+    typedef decltype(s) S;
+#define DIVN(SEC)                                                                                          \
+  hipLaunchKernelGGL((k_divide_narrow<S, SEC>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab,      \
+                     (const double*)h->arena, (typename S::elem*)d_out, tpp)
+    if (h->secure) DIVN(true);
+    else DIVN(false);
 #undef DIVN
+  });
   HIP_TRY(h, hipGetLastError());
   return IPLS_OK;
 }
@@ -2421,15 +2387,13 @@ int dev_load_model(ipls_dev* h, const void* src, int64_t n, int src_kind) {
   for (int p = 0; p < h->P; ++p) {
     const int64_t L = h->len[p];
     // IPLS.java:1883-1895: values for j < min((i+1)c, M), count slot 0.0
-    if (fmt == kFmtF32)
-      hipLaunchKernelGGL(k_load_model_f32, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, (const float*)d,
-                         h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
-    else if (fmt == kFmtF16)
-      hipLaunchKernelGGL(k_load_model_h16<FmtF16>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream,
-                         (const unsigned short*)d, h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
-    else if (fmt == kFmtBF16)
-      hipLaunchKernelGGL(k_load_model_h16<FmtBF16>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream,
-                         (const unsigned short*)d, h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+    if (fmt_trainer(fmt))
+      with_narrow(fmt, [&](auto s) {
+        typedef decltype(s) S;
+        hipLaunchKernelGGL(k_load_model_narrow<S>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream,
+                           (const typename S::elem*)d, h->flat_off[p] - h->flat_base, L - 1, L,
+                           h->arena + h->w_off[p]);
+      });
     else if (be)
       hipLaunchKernelGGL(k_load_model<true>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, d,
                          h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
@@ -2511,23 +2475,20 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
     if (vec) hipLaunchKernelGGL((k_split<BI, BO, 0, true>), g, dim3(kBlock), 0, h->stream, d, (int64_t)0, ncopy, L, out); \
     else hipLaunchKernelGGL((k_split<BI, BO, 0, false>), g, dim3(kBlock), 0, h->stream, d, (int64_t)0, ncopy, L, out); \
   } while (0)
-#define SPLF(BO)                                                                                                 \
+#define SPLN(BO)                                                                                                 \
   do {                                                                                                           \
-    if (vec) hipLaunchKernelGGL((k_split_f32<BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const float*)d, (int64_t)0, ncopy, L, out); \
-    else hipLaunchKernelGGL((k_split_f32<BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const float*)d, (int64_t)0, ncopy, L, out); \
+    if (vec) hipLaunchKernelGGL((k_split_narrow<S, BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, (int64_t)0, ncopy, L, out); \
+    else hipLaunchKernelGGL((k_split_narrow<S, BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, (int64_t)0, ncopy, L, out); \
   } while (0)
-#define SPLH(H, BO)                                                                                              \
-  do {                                                                                                           \
-    if (vec) hipLaunchKernelGGL((k_split_h16<H, BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, (int64_t)0, ncopy, L, out); \
-    else hipLaunchKernelGGL((k_split_h16<H, BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, (int64_t)0, ncopy, L, out); \
-  } while (0)
-  if (fmt == kFmtF32) { if (be_out) SPLF(true); else SPLF(false); }
-  else if (fmt == kFmtF16) { if (be_out) SPLH(FmtF16, true); else SPLH(FmtF16, false); }
-  else if (fmt == kFmtBF16) { if (be_out) SPLH(FmtBF16, true); else SPLH(FmtBF16, false); }
+  if (fmt_trainer(fmt))
+    with_narrow(fmt, [&](auto s) {
+      typedef decltype(s) S;
+      if (be_out) SPLN(true);
+      else SPLN(false);
+    });
   else if (be_in) { if (be_out) SPL(true, true); else SPL(true, false); }
   else { if (be_out) SPL(false, true); else SPL(false, false); }
-#undef SPLH
-#undef SPLF
+#undef SPLN
 #undef SPL
   HIP_TRY(h, hipGetLastError());
   if (host_out) return d2h(h, dst, out, (size_t)L * 8);
@@ -2603,23 +2564,20 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     if (vec) hipLaunchKernelGGL((k_split<BI, false, M, true>), g, dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc); \
     else hipLaunchKernelGGL((k_split<BI, false, M, false>), g, dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc); \
   } while (0)
-#define UPDF(M)                                                                                                 \
+#define UPDN(M)                                                                                                 \
   do {                                                                                                          \
-    if (vec) hipLaunchKernelGGL((k_split_f32<false, M, true>), g, dim3(kBlock), 0, h->stream, (const float*)d, lo, nc[p], L, acc); \
-    else hipLaunchKernelGGL((k_split_f32<false, M, false>), g, dim3(kBlock), 0, h->stream, (const float*)d, lo, nc[p], L, acc); \
+    if (vec) hipLaunchKernelGGL((k_split_narrow<S, false, M, true>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, lo, nc[p], L, acc); \
+    else hipLaunchKernelGGL((k_split_narrow<S, false, M, false>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, lo, nc[p], L, acc); \
   } while (0)
-#define UPDH(H, M)                                                                                              \
-  do {                                                                                                          \
-    if (vec) hipLaunchKernelGGL((k_split_h16<H, false, M, true>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, lo, nc[p], L, acc); \
-    else hipLaunchKernelGGL((k_split_h16<H, false, M, false>), g, dim3(kBlock), 0, h->stream, (const unsigned short*)d, lo, nc[p], L, acc); \
-  } while (0)
-    if (fmt == kFmtF32) { if (zero) UPDF(2); else UPDF(1); }
-    else if (fmt == kFmtF16) { if (zero) UPDH(FmtF16, 2); else UPDH(FmtF16, 1); }
-    else if (fmt == kFmtBF16) { if (zero) UPDH(FmtBF16, 2); else UPDH(FmtBF16, 1); }
+    if (fmt_trainer(fmt))
+      with_narrow(fmt, [&](auto s) {
+        typedef decltype(s) S;
+        if (zero) UPDN(2);
+        else UPDN(1);
+      });
     else if (be) { if (zero) UPD(true, 2); else UPD(true, 1); }
     else { if (zero) UPD(false, 2); else UPD(false, 1); }
-#undef UPDH
-#undef UPDF
+#undef UPDN
 #undef UPD
     HIP_TRY(h, hipGetLastError());
     h->agg_zero[p] = 0;

@@ -48,14 +48,6 @@
 
 namespace {
 
-// Output kinds narrowed on the device (include/ipls_agg.h): floats, halves, bfloat16s.
-constexpr bool narrow_dev(int kind) { return kind == IPLS_DEV_F32 || kind == IPLS_DEV_F16 || kind == IPLS_DEV_BF16; }
-constexpr bool narrow_host(int kind) { return kind == IPLS_HOST_F32 || kind == IPLS_HOST_F16 || kind == IPLS_HOST_BF16; }
-// bytes per output value of a get_partitions / aggregate_round kind
-constexpr int64_t narrow_esz(int kind) {
-  return (kind == IPLS_DEV_F32 || kind == IPLS_HOST_F32) ? 4 : (narrow_dev(kind) || narrow_host(kind)) ? 2 : 8;
-}
-
 // A replica slot's partial sum of one partition (on the slot's device).
 struct Partial {
   double* d = nullptr;
@@ -921,16 +913,16 @@ int ipls_agg_aggregate_round(ipls_agg* H, int p_first, int n_parts, const void* 
     const int q0 = std::max(p_first, H->lo[s]), q1 = std::min(p_first + n_parts, H->lo[s + 1]);
     // the averages of partition q land at flat offset off[q] - off[p_first]
     // (4 B per value for the float kinds, 2 B for the half and bfloat16 kinds)
-    const int64_t esz = narrow_esz(avg_kind);
+    const int64_t esz = fmt_size(kind_fmt(avg_kind));
     void* a = avg_out ? (void*)((char*)avg_out + esz * (H->off[q0] - H->off[p_first])) : nullptr;
     return dev_aggregate_round(H->sh[s], q0 - H->lo[s], q1 - q0, bufs + (size_t)(q0 - p_first) * k, k, src_kind, a,
                                avg_kind);
   };
-  if (avg_out && (avg_kind == IPLS_DEV_F64 || narrow_dev(avg_kind)))
+  if (avg_out && (avg_kind == IPLS_DEV_F64 || kind_trainer_dev(avg_kind)))
     for (int s : ss)   // each shard writes its partitions' averages into avg_out
       if (int rc = check_reach(H, s, avg_out, "averages buffer")) return rc;
   H->last_shard = ss.back();
-  if (avg_out && (avg_kind == IPLS_HOST_F64 || narrow_host(avg_kind))) return par_shards(H, ss, one);   // each shard copies its averages back
+  if (avg_out && (avg_kind == IPLS_HOST_F64 || kind_trainer_host(avg_kind))) return par_shards(H, ss, one);   // each shard copies its averages back
   for (int s : ss)
     if (int rc = fwd(H, s, one(s))) return rc;
   return IPLS_OK;
@@ -1039,16 +1031,16 @@ int ipls_agg_get_partitions(ipls_agg* H, void* out, int64_t n, int out_kind) {
   if (H->S() == 1) return fwd(H, 0, dev_get_partitions(H->sh[0], out, n, out_kind));
   if (n < H->flat_total)
     return ferr(H, IPLS_E_RANGE, "output of %lld < model size %lld", (long long)n, (long long)H->flat_total);
-  const bool narrow_out = narrow_dev(out_kind) || narrow_host(out_kind);
+  const bool narrow_out = kind_trainer(out_kind);
   if (out_kind != IPLS_HOST_F64 && out_kind != IPLS_HOST_BE_CANON && out_kind != IPLS_DEV_F64 && !narrow_out)
     return ferr(H, IPLS_E_INVAL, "bad out_kind %d", out_kind);
-  if (out_kind == IPLS_DEV_F64 || narrow_dev(out_kind))
+  if (out_kind == IPLS_DEV_F64 || kind_trainer_dev(out_kind))
     for (int s : nonempty_shards(H))
       if (int rc = check_reach(H, s, out, "model buffer")) return rc;
   // every shard writes its flat segment [off[lo_s], ...) of the model
   return par_shards(H, nonempty_shards(H), [&](int s) {
     const int64_t base = H->off[H->lo[s]];
-    return dev_get_partitions(H->sh[s], (char*)out + narrow_esz(out_kind) * base, n - base, out_kind);
+    return dev_get_partitions(H->sh[s], (char*)out + fmt_size(kind_fmt(out_kind)) * base, n - base, out_kind);
   });
 }
 

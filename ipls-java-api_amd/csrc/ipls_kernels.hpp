@@ -1500,356 +1500,113 @@ __global__ __launch_bounds__(kBlock) void k_ser_unbox(const unsigned char* __res
 }
 
 // ===========================================================================
-// float32 trainer boundary (Model.java:423 widens a float INDArray to the
-// doubles it hands to UpdateGradient; Model.java:388-390 narrows GetPartitions'
-// doubles back into one).  Sources are read as floats and widened in registers
-// -- (double)f is exact, subnormals included (the kernels keep f32 denormals:
-// no flush flag anywhere) -- then every expression is the f64 kernel's, so the
-// bits are those of the f64 path fed the widened values.  Outputs are the f64
-// quotient rounded once to float (v_cvt_f32_f64, ties to even).
+// Trainer boundary: sources and outputs narrower than a double.  float32
+// (Model.java:423 widens a float INDArray to the doubles it hands to
+// UpdateGradient; Model.java:388-390 narrows GetPartitions' doubles back into
+// one) and the two 16-bit formats a trainer under autocast (or a DL4J network
+// built with DataType.HALF / BFLOAT16) holds.  One kernel per job, with the
+// format as a template parameter S (FmtF32, FmtF16, FmtBF16).
+// Sources: v = (double)src[i] in registers -- a float directly, binary16 by
+// f16 -> f32 -> f64, bfloat16 by (bits << 16) taken as an f32 -> f64; every
+// step is exact, subnormals included (no flush flag anywhere: a bf16 subnormal
+// is an f32 subnormal) -- then every expression is the f64 kernel's, so the
+// bits are those of the f64 path fed the widened values.
+// Outputs: the f64 quotient rounded once to float (v_cvt_f32_f64, ties to
+// even), and for a 16-bit format that float rounded to the format (ties to
+// even, overflow to +-inf, subnormals kept, -0.0 kept, NaN stays NaN): two
+// roundings, what a trainer gets when it narrows the f32 output itself.
+//
+// A format supplies:
+//   elem, raw        the element type of a buffer; one loaded element
+//   Vec<E>, ldv<E>   E consecutive elements as loaded by one non-temporal load
+//   get<E>(v, c)     element c of such a vector, widened
+//   unpack(v)        such a vector as a lane of the fold keeps it until the adds
+//   ldraw, widen     the scalar load and its widening
+//   narrow(float)    the element's bit pattern for a float; put stores one
+//   kPeersVec<E>     peers in flight on the fold's partial-tile vector steps
 // ===========================================================================
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef const IPLS_GLOBAL f4* gcf4;
-typedef IPLS_GLOBAL f4* gf4;
-typedef const IPLS_GLOBAL float* gcf32;
 
-__device__ __forceinline__ f4 ld16f(const float* p) { return __builtin_nontemporal_load((gcf4)p); }
-__device__ __forceinline__ float ld4f(const float* p) { return *(gcf32)p; }
+// 4 floats of one load as the fold keeps them between the load and the adds: unpacked, like
+// HWords.  Kept as one float4 value, hipcc carries the fold's prefetched peer as 64-bit pairs and
+// the fold at config C measured 0.3-0.5 % slower (profiles/narrow_unify/float4_fold/).  The split
+// keeps the float4: unpacked there, its accumulate form measured 0.3 % slower
+// (profiles/narrow_unify/unpacked_split/).
+struct FQuad {
+  float f[4];
+};
+struct FmtF32 {
+  typedef float elem;
+  typedef float raw;
+  template <int E>
+  using Vec = f4;
+  template <int E>
+  static constexpr int kPeersVec = 8;
+  template <int E>
+  static __device__ __forceinline__ f4 ldv(const float* p) {
+    static_assert(E == 4, "floats come 4 to a 16-B load");
+    return __builtin_nontemporal_load((const IPLS_GLOBAL f4*)p);
+  }
+  static __device__ __forceinline__ FQuad unpack(const f4& t) { return FQuad{{t.x, t.y, t.z, t.w}}; }
+  template <int E>
+  static __device__ __forceinline__ double get(const f4& v, int c) { return (double)v[c]; }
+  template <int E>
+  static __device__ __forceinline__ double get(const FQuad& v, int c) { return (double)v.f[c]; }
+  static __device__ __forceinline__ float ldraw(const float* p) { return *(const IPLS_GLOBAL float*)p; }
+  static __device__ __forceinline__ double widen(float f) { return (double)f; }
+  // the caller's (float)d is the output: nothing more to round
+  static __device__ __forceinline__ unsigned narrow(float f) { return __builtin_bit_cast(unsigned, f); }
+  static __device__ __forceinline__ void put(float* p, unsigned b) { *p = __builtin_bit_cast(float, b); }
+};
 
-// ---------------------------------------------------------------------------
-// k_reduce_f32: the batched fixed-order fold (k_reduce) over f32 buckets.
-// Grid = n_parts * tiles_per_part blocks of BS lanes; a tile is BS * 4 * R
-// elements.  A lane owns 4 consecutive elements per vector: one 16-B
-// non-temporal load per peer per vector, four widenings, four chained f64
-// adds into 4 accumulators, two 16-B stores (native doubles, or BE_OUT bytes).
-// The peer axis is walked in order per element, as in reduce_tiles.
-//   VEC : every bucket and every destination of the launch is 16-B aligned
-//         (decided by the host); full tiles then take the vector path and the
-//         partial last tile 4*BS-element vector steps with a scalar remainder.
-//         !VEC: everything element by element (buckets at 4 mod 16 etc.).
-//   MAP : 0 partition-major, 3 partial tiles first (map_block).
-//   PF  : 1 = peer j+1's R loads are issued before peer j's values are added
-//         (two peers' loads in flight per lane, the fold order unchanged).
-// ACCUM reads the target in BE_OUT's byte order, like k_reduce.
-// ---------------------------------------------------------------------------
-template <bool BE_OUT, int START, int R, int BS, int MAP, bool VEC, int PF = 0>
-__global__ __launch_bounds__(BS) void k_reduce_f32(const float* const* __restrict__ bufs,
-                                                   const PartDesc* __restrict__ parts, int k, int tiles_per_part,
-                                                   int n_parts) {
-  constexpr int64_t kTile = (int64_t)BS * 4 * R;
-  constexpr int kPB = 8;   // peers in flight on the partial-tile paths
-  int q, t;
-  map_block(MAP, gridDim.x, tiles_per_part, n_parts, q, t);
-  if (q >= n_parts) return;
-  const int64_t L = parts[q].len;
-  const int64_t base = (int64_t)t * kTile;
-  if (base >= L) return;
-  unsigned long long* __restrict__ dst = parts[q].dst;
-  const float* const* __restrict__ pb = bufs + (size_t)q * k;
-  const int tid = threadIdx.x;
-  const int j0 = (START == kFirst) ? 1 : 0;
-
-  if (VEC && base + kTile <= L) {
-    // lane's first element of the tile; vector r is r * BS * 4 elements on
-    const int64_t o0 = base + 4 * (int64_t)tid;
-    double acc[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int64_t o = o0 + (int64_t)r * BS * 4;
-      if constexpr (START == kZero) {
-        acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
-      } else if constexpr (START == kFirst) {
-        const f4 x = ld16f(pb[0] + o);
-        acc[r][0] = (double)x.x;
-        acc[r][1] = (double)x.y;
-        acc[r][2] = (double)x.z;
-        acc[r][3] = (double)x.w;
-      } else {
-        const d2 a = decode2<BE_OUT>(ld16<false>(dst + o));
-        const d2 b = decode2<BE_OUT>(ld16<false>(dst + o + 2));
-        acc[r][0] = a.x;
-        acc[r][1] = a.y;
-        acc[r][2] = b.x;
-        acc[r][3] = b.y;
-      }
-    }
-    if constexpr (PF) {
-      f4 v[R];
-      if (j0 < k) {
-        const float* __restrict__ src = pb[j0] + o0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = ld16f(src + (int64_t)r * BS * 4);
-      }
-      for (int j = j0; j < k; ++j) {
-        f4 nx[R];
-        if (j + 1 < k) {
-          const float* __restrict__ src = pb[j + 1] + o0;
-#pragma unroll
-          for (int r = 0; r < R; ++r) nx[r] = ld16f(src + (int64_t)r * BS * 4);
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          acc[r][0] = acc[r][0] + (double)v[r].x;
-          acc[r][1] = acc[r][1] + (double)v[r].y;
-          acc[r][2] = acc[r][2] + (double)v[r].z;
-          acc[r][3] = acc[r][3] + (double)v[r].w;
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = nx[r];
-      }
+// E consecutive 16-bit elements as E / 2 words: one 8-B (E = 4) or 16-B (E = 8) non-temporal load
+template <int E>
+struct HWords {
+  unsigned w[E / 2];
+};
+// what the two 16-bit formats share; D supplies widen, lo / hi (the two elements of a word) and narrow
+template <class D>
+struct Fmt16 {
+  typedef unsigned short elem;
+  typedef unsigned short raw;
+  template <int E>
+  using Vec = HWords<E>;
+  // 64 B per lane in flight (8 peers of 16 B next to 8 f64 accumulators spill at 1024 lanes)
+  template <int E>
+  static constexpr int kPeersVec = 32 / E;
+  template <int E>
+  static __device__ __forceinline__ HWords<E> ldv(const unsigned short* p) {
+    HWords<E> r;
+    if constexpr (E == 8) {
+      const u4w t = __builtin_nontemporal_load((const IPLS_GLOBAL u4w*)p);
+      r.w[0] = t.x, r.w[1] = t.y, r.w[2] = t.z, r.w[3] = t.w;
     } else {
-    for (int j = j0; j < k; ++j) {
-      const float* __restrict__ src = pb[j] + o0;
-      f4 v[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) v[r] = ld16f(src + (int64_t)r * BS * 4);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        acc[r][0] = acc[r][0] + (double)v[r].x;
-        acc[r][1] = acc[r][1] + (double)v[r].y;
-        acc[r][2] = acc[r][2] + (double)v[r].z;
-        acc[r][3] = acc[r][3] + (double)v[r].w;
-      }
+      static_assert(E == 4, "4 or 8 elements per load");
+      typedef unsigned u2w __attribute__((ext_vector_type(2)));
+      const u2w t = __builtin_nontemporal_load((const IPLS_GLOBAL u2w*)p);
+      r.w[0] = t.x, r.w[1] = t.y;
     }
-    }  // !PF
-    // A lane's 4 sums are 32 B, so its own two 16-B stores would each cover
-    // half of every 128-B line the wave writes (measured: WRITE_SIZE 1.12x the
-    // algorithmic 8 L).  Instead the 8 lanes that own two adjacent lines
-    // (lanes 0-3 the first, 4-7 the second) swap their upper pair of sums
-    // with lane ^ 4: the first store instruction then writes the first line
-    // whole -- lanes 0-3 their own lower pairs, lanes 4-7 the upper pairs of
-    // lanes 0-3 -- and the second one the second line.  Values only move
-    // between lanes; every sum is unchanged.
-    const bool hi = tid & 4;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int64_t o = o0 + (int64_t)r * BS * 4;
-      const d2 own = d2{acc[r][0], acc[r][1]};
-      const d2 got = d2{__shfl_xor(acc[r][2], 4), __shfl_xor(acc[r][3], 4)};   // elements o ^ 16 .. + 2, + 3
-      __builtin_nontemporal_store(encode2<BE_OUT>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
-      __builtin_nontemporal_store(encode2<BE_OUT>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
-    }
-    return;
+    return r;
   }
-  // ------- partial last tile, or a launch with a misaligned operand -------
-  const int64_t end = base + kTile < L ? base + kTile : L;
-  int64_t sb = base;
-  if constexpr (VEC) {
-    for (; sb + 4 * BS <= end; sb += 4 * BS) {
-      const int64_t o = sb + 4 * (int64_t)tid;
-      double a0, a1, a2, a3;
-      if constexpr (START == kZero) {
-        a0 = a1 = a2 = a3 = 0.0;
-      } else if constexpr (START == kFirst) {
-        const f4 x = ld16f(pb[0] + o);
-        a0 = (double)x.x, a1 = (double)x.y, a2 = (double)x.z, a3 = (double)x.w;
-      } else {
-        const d2 a = decode2<BE_OUT>(ld16<false>(dst + o));
-        const d2 b = decode2<BE_OUT>(ld16<false>(dst + o + 2));
-        a0 = a.x, a1 = a.y, a2 = b.x, a3 = b.y;
-      }
-      int jj = j0;
-      for (; jj + kPB <= k; jj += kPB) {
-        f4 v[kPB];
-#pragma unroll
-        for (int g = 0; g < kPB; ++g) v[g] = ld16f(pb[jj + g] + o);
-#pragma unroll
-        for (int g = 0; g < kPB; ++g) {
-          a0 = a0 + (double)v[g].x;
-          a1 = a1 + (double)v[g].y;
-          a2 = a2 + (double)v[g].z;
-          a3 = a3 + (double)v[g].w;
-        }
-      }
-      for (; jj < k; ++jj) {
-        const f4 x = ld16f(pb[jj] + o);
-        a0 = a0 + (double)x.x;
-        a1 = a1 + (double)x.y;
-        a2 = a2 + (double)x.z;
-        a3 = a3 + (double)x.w;
-      }
-      __builtin_nontemporal_store(encode2<BE_OUT>(d2{a0, a1}), (gu2)(dst + o));
-      __builtin_nontemporal_store(encode2<BE_OUT>(d2{a2, a3}), (gu2)(dst + o + 2));
-    }
+  template <int E>
+  static __device__ __forceinline__ const HWords<E>& unpack(const HWords<E>& v) { return v; }
+  template <int E>
+  static __device__ __forceinline__ double get(const HWords<E>& v, int c) {
+    return (c & 1) ? D::hi(v.w[c >> 1]) : D::lo(v.w[c >> 1]);
   }
-  for (int64_t e = sb + tid; e < end; e += BS) {
-    double acc;
-    if constexpr (START == kZero) acc = 0.0;
-    else if constexpr (START == kFirst) acc = (double)ld4f(pb[0] + e);
-    else acc = decode1<BE_OUT>(ld8(dst + e));
-    int jj = j0;
-    for (; jj + kPB <= k; jj += kPB) {
-      float v[kPB];
-#pragma unroll
-      for (int g = 0; g < kPB; ++g) v[g] = ld4f(pb[jj + g] + e);
-#pragma unroll
-      for (int g = 0; g < kPB; ++g) acc = acc + (double)v[g];
-    }
-    for (; jj < k; ++jj) acc = acc + (double)ld4f(pb[jj] + e);
-    st8(dst + e, BE_OUT ? f64_to_be(acc) : __builtin_bit_cast(unsigned long long, acc));
+  static __device__ __forceinline__ unsigned short ldraw(const unsigned short* p) {
+    return *(const IPLS_GLOBAL unsigned short*)p;
   }
-}
-
-// Shape of the f32-source elementwise kernels when the partition's slice of
-// the flat vector and its destination are both 16-B aligned (VEC, decided by
-// the host per partition: flat + p*chunk is only 4-B aligned in general): a
-// block owns kEwTile consecutive elements, a lane kEwV32 vectors of 4 floats.
-constexpr int kEwV32 = 2;
-static_assert((int64_t)kBlock * 4 * kEwV32 == kEwTile, "one elementwise tile size");
-
-// k_split over a float flat vector: OrganizeGradients (MODE 0) and
-// UpdateGradient's own accumulate (MODE 1, 2), the expressions of k_split on
-// v = (double)flat[lo + i].  The tile that holds the count slot (1.0, what a
-// widened 1.0f count slot is) goes element by element.
-template <bool BE_OUT, int MODE, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_split_f32(const float* __restrict__ flat, int64_t lo, int64_t ncopy,
-                                                      int64_t L, unsigned long long* __restrict__ dst) {
-  static_assert(MODE == 0 || !BE_OUT, "the folds write native doubles");
-  auto one = [&](int64_t i) {
-    double v;
-    if (i < ncopy) v = (double)ld4f(flat + lo + i);
-    else if (i == ncopy) v = 1.0;
-    else v = 0.0;
-    if constexpr (MODE == 1) {
-      const double a = __builtin_bit_cast(double, dst[i]);
-      dst[i] = __builtin_bit_cast(unsigned long long, a + v);
-    } else if constexpr (MODE == 2) {
-      dst[i] = __builtin_bit_cast(unsigned long long, 0.0 + v);
-    } else {
-      dst[i] = BE_OUT ? f64_to_be(v) : __builtin_bit_cast(unsigned long long, v);
-    }
-  };
-  if constexpr (VEC) {
-    const int64_t base = (int64_t)blockIdx.x * kEwTile;
-    if (base + kEwTile <= ncopy) {
-      const float* src = flat + lo;
-      f4 sv[kEwV32];
-      u2 dv[kEwV32][2];
-#pragma unroll
-      for (int k = 0; k < kEwV32; ++k) {
-        const int64_t i = base + 4 * ((int64_t)k * kBlock + threadIdx.x);
-        sv[k] = ld16f(src + i);
-        if constexpr (MODE == 1) {
-          dv[k][0] = *(gcu2)(dst + i);
-          dv[k][1] = *(gcu2)(dst + i + 2);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kEwV32; ++k) {
-        const int64_t i = base + 4 * ((int64_t)k * kBlock + threadIdx.x);
-        const d2 x0 = d2{(double)sv[k].x, (double)sv[k].y}, x1 = d2{(double)sv[k].z, (double)sv[k].w};
-        d2 o0, o1;
-        if constexpr (MODE == 1) {
-          const d2 a0 = __builtin_bit_cast(d2, dv[k][0]), a1 = __builtin_bit_cast(d2, dv[k][1]);
-          o0 = d2{a0.x + x0.x, a0.y + x0.y};
-          o1 = d2{a1.x + x1.x, a1.y + x1.y};
-        } else if constexpr (MODE == 2) {
-          o0 = d2{0.0 + x0.x, 0.0 + x0.y};
-          o1 = d2{0.0 + x1.x, 0.0 + x1.y};
-        } else {
-          o0 = x0;
-          o1 = x1;
-        }
-        *(gu2)(dst + i) = encode2<BE_OUT>(o0);
-        *(gu2)(dst + i + 2) = encode2<BE_OUT>(o1);
-      }
-      return;
-    }
-    const int64_t end = base + kEwTile < L ? base + kEwTile : L;
-    for (int64_t i = base + threadIdx.x; i < end; i += kBlock) one(i);
-  } else {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < L) one(i);
+  static __device__ __forceinline__ void put(unsigned short* p, unsigned b) {
+    *(IPLS_GLOBAL unsigned short*)p = (unsigned short)b;
   }
-}
-
-// k_load_model over a float model (InitializeWeights from model.params()).
-__global__ __launch_bounds__(kBlock) void k_load_model_f32(const float* __restrict__ flat, int64_t lo, int64_t ncopy,
-                                                           int64_t L, double* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= L) return;
-  dst[i] = (i < ncopy) ? (double)ld4f(flat + lo + i) : 0.0;
-}
-
-// ---------------------------------------------------------------------------
-// k_divide_f32: the GetPartitions divide (k_divide) narrowed to float:
-//   out[m] = (float)(cnt == 0.0 ? W[p][j] : W[p][j] / den)
-// The quotient is k_divide's IEEE double division; it is rounded once to
-// float (ties to even; overflow to +-inf, subnormals kept, -0.0 stays -0.0).
-// Never an f32 division, never a reciprocal.  Tiles are laid over the OUTPUT
-// as in k_divide: block 0 writes the `head` floats up to the first 128-B line
-// of this partition's output (p*chunk floats is arbitrary mod 4), then every
-// lane stores 16 B = 4 floats and a wave whole lines (64 x 16 B = 8 lines); W
-// is read with 8-B loads (its alignment against the output is arbitrary).
-// ---------------------------------------------------------------------------
-constexpr int kDivV32 = 2;
-constexpr int64_t kDivTile32 = (int64_t)kBlock * 4 * kDivV32;
-
-template <bool SECURE, int BS = kBlock, int V = kDivV32>
-__global__ __launch_bounds__(BS) void k_divide_f32(const DivDesc* __restrict__ parts, const double* __restrict__ arena,
-                                                   float* __restrict__ out, int tiles_per_part) {
-  constexpr int64_t kTile = (int64_t)BS * 4 * V;
-  static_assert(BS % 64 == 0, "whole waves");
-  const int q = blockIdx.x / tiles_per_part;
-  const int t = blockIdx.x - q * tiles_per_part;
-  const DivDesc d = parts[q];
-  const int64_t n = d.len - 1;
-  const double* w = arena + d.w_off;
-  const double cnt = w[d.len - 1];
-  const double den = SECURE ? 1e12 * cnt : cnt;   // IPLS.java:1167
-  auto f = [&](double x) -> float { return (float)((cnt == 0.0) ? x : x / den); };
-  float* o = out + d.out_off;
-  const int64_t to_line = (32 - (int64_t)(((uintptr_t)o >> 2) & 31)) & 31;   // floats to a 128-B boundary
-  const int64_t head = to_line < n ? to_line : n;
-  if (t == 0 && threadIdx.x < head) o[threadIdx.x] = f(w[threadIdx.x]);
-  const int64_t base = (int64_t)t * kTile + head;
-  if (base >= n) return;
-  if (base + kTile <= n) {
-    // wave (threadIdx.x / 64) owns [base + wave * 256 * V, + 256 * V)
-    const int64_t wave_base = base + (int64_t)(threadIdx.x >> 6) * 256 * V + 4 * (threadIdx.x & 63);
-    double x[V][4];
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const int64_t i = wave_base + (int64_t)v * 256;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        x[v][c] = __builtin_nontemporal_load((const __attribute__((address_space(1))) double*)(w + i + c));
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const int64_t i = wave_base + (int64_t)v * 256;
-      const f4 y = f4{f(x[v][0]), f(x[v][1]), f(x[v][2]), f(x[v][3])};
-      __builtin_nontemporal_store(y, (gf4)(o + i));
-    }
-    return;
+};
+struct FmtF16 : Fmt16<FmtF16> {     // IEEE binary16
+  static __device__ __forceinline__ double widen(unsigned short b) {
+    return (double)(float)__builtin_bit_cast(_Float16, b);
   }
-  for (int64_t i = base + threadIdx.x; i < n; i += BS) o[i] = f(w[i]);
-}
-
-// ===========================================================================
-// half-precision trainer boundary: the float32 boundary above for the two
-// 16-bit formats a trainer under autocast (or a DL4J network built with
-// DataType.HALF / BFLOAT16) holds.  One template parameter H names the format.
-// Sources: v = (double)src[i] -- binary16 by f16 -> f32 -> f64 (both steps
-// exact, subnormals kept), bfloat16 by (bits << 16) taken as an f32 -> f64
-// (exact; a bf16 subnormal is an f32 subnormal) -- then every expression is the
-// f64 kernel's.  Outputs: the f64 quotient rounded to float as k_divide_f32
-// does, then that float rounded to the 16-bit format (ties to even, overflow to
-// +-inf, subnormals kept, -0.0 kept, NaN stays NaN): two roundings, what a
-// trainer gets when it narrows the f32 output itself.  No flush-to-zero: both
-// denormal modes stay on, as in the f32 kernels.
-// ===========================================================================
-typedef unsigned u2w __attribute__((ext_vector_type(2)));
-typedef const IPLS_GLOBAL u2w* gcu2w;
-typedef const IPLS_GLOBAL u4w* gcu4w;
-typedef IPLS_GLOBAL u4w* gu4w;
-typedef const IPLS_GLOBAL unsigned short* gcu16;
-typedef IPLS_GLOBAL unsigned short* gu16;
-
-struct FmtF16 {    // IEEE binary16
-  static __device__ __forceinline__ double one(unsigned short b) { return (double)(float)__builtin_bit_cast(_Float16, b); }
-  static __device__ __forceinline__ double lo(unsigned w) { return one((unsigned short)(w & 0xffffu)); }
-  static __device__ __forceinline__ double hi(unsigned w) { return one((unsigned short)(w >> 16)); }
+  static __device__ __forceinline__ double lo(unsigned w) { return widen((unsigned short)(w & 0xffffu)); }
+  static __device__ __forceinline__ double hi(unsigned w) { return widen((unsigned short)(w >> 16)); }
   // v_cvt_f16_f32.  The caller's (float)d must stay a rounding of its own (v_cvt_f32_f64): the library is built
   // with -ffp-contract=off -fno-fast-math, under which hipcc keeps both; without them it folds the pair into one
   // f64 -> f16 sequence, a single rounding (test_get_partitions_h16's 0x3c00 quotient fails then).
@@ -1857,8 +1614,8 @@ struct FmtF16 {    // IEEE binary16
     return __builtin_bit_cast(unsigned short, (_Float16)f);
   }
 };
-struct FmtBF16 {   // bfloat16: the upper half of an f32
-  static __device__ __forceinline__ double one(unsigned short b) {
+struct FmtBF16 : Fmt16<FmtBF16> {   // bfloat16: the upper half of an f32
+  static __device__ __forceinline__ double widen(unsigned short b) {
     return (double)__builtin_bit_cast(float, (unsigned)b << 16);
   }
   static __device__ __forceinline__ double lo(unsigned w) { return (double)__builtin_bit_cast(float, w << 16); }
@@ -1868,60 +1625,48 @@ struct FmtBF16 {   // bfloat16: the upper half of an f32
   }
 };
 
-__device__ __forceinline__ unsigned short ld2h(const unsigned short* p) { return *(gcu16)p; }
-// E consecutive 16-bit elements as E / 2 words: one 8-B (E = 4) or 16-B (E = 8) non-temporal load
-template <int E>
-struct HWords {
-  unsigned w[E / 2];
-};
-template <int E>
-__device__ __forceinline__ HWords<E> ldvh(const unsigned short* p) {
-  HWords<E> r;
-  if constexpr (E == 8) {
-    const u4w t = __builtin_nontemporal_load((gcu4w)p);
-    r.w[0] = t.x, r.w[1] = t.y, r.w[2] = t.z, r.w[3] = t.w;
-  } else {
-    static_assert(E == 4, "4 or 8 elements per load");
-    const u2w t = __builtin_nontemporal_load((gcu2w)p);
-    r.w[0] = t.x, r.w[1] = t.y;
-  }
-  return r;
-}
-
 // ---------------------------------------------------------------------------
-// k_reduce_h16: the batched fixed-order fold (k_reduce_f32's contract) over
-// 16-bit buckets.  Grid = n_parts * tiles_per_part blocks of BS lanes; a tile
+// k_reduce_narrow: the batched fixed-order fold (k_reduce) over buckets of a
+// narrow format.  Grid = n_parts * tiles_per_part blocks of BS lanes; a tile
 // is BS * E * R elements.  A lane owns E consecutive elements per vector: one
-// load per peer per vector, E widenings, E chained f64 adds into E
-// accumulators.  The peer axis is walked in order per element.
-//   E   : 4 is what the library instantiates (with XP = 1).  E = 8 and XP = 0
-//         exist for tools/reduce_h16_sweep.hip only: the layout that lost the
-//         sweep and the no-exchange baselines, kept so that the sweep recorded
-//         in DESIGN.md 3.5.1 can be re-run on the same kernel body.
-//         8 = 16-B loads; the lane's 8 sums are 64 B, so the 8 lanes that own
-//         four adjacent 128-B lines transpose their 16-B pairs among
-//         themselves (two butterfly steps, lane ^ 4 then lane ^ 2) and every
-//         store instruction writes whole lines.
-//         4 = 8-B loads with k_reduce_f32's lane ^ 4 swap unchanged.
-//   VEC : every bucket and destination of the launch is 16-B aligned (decided
-//         by the host); full tiles take the vector path, the partial last tile
-//         E*BS-element vector steps and a scalar remainder.  !VEC: everything
-//         element by element (2-B loads, 8 peers in flight).
+// non-temporal load per peer per vector, E widenings, E chained f64 adds into
+// E accumulators, E / 2 16-B stores (native doubles, or BE_OUT bytes).  The
+// peer axis is walked in order per element, as in reduce_tiles.
+//   E   : 4 is what the library instantiates (with XP = 1): 16-B loads of
+//         floats, 8-B loads of 16-bit elements, and the lane ^ 4 swap below
+//         before the stores.  Floats have no other layout.  E = 8 and XP = 0
+//         exist for 16-bit sources and tools/reduce_h16_sweep.hip only: the
+//         layout that lost the sweep and the no-exchange baselines, kept so
+//         that the sweep recorded in DESIGN.md 3.5.1 can be re-run on the same
+//         kernel body.  8 = 16-B loads; the lane's 8 sums are 64 B, so the 8
+//         lanes that own four adjacent 128-B lines transpose their 16-B pairs
+//         among themselves (two butterfly steps, lane ^ 4 then lane ^ 2) and
+//         every store instruction writes whole lines.
+//   VEC : every bucket and every destination of the launch is 16-B aligned
+//         (decided by the host); full tiles then take the vector path and the
+//         partial last tile E*BS-element vector steps with a scalar remainder.
+//         !VEC: everything element by element (buckets at 4 mod 16 etc.;
+//         element-sized loads, 8 peers in flight).
 //   MAP : 0 partition-major, 3 partial tiles first (map_block).
-//   PF  : 1 = peer j+1's loads are issued before peer j's values are added.
+//   PF  : 1 = peer j+1's R loads are issued before peer j's values are added
+//         (two peers' loads in flight per lane, the fold order unchanged).
 //   XP  : 0 = no exchange between lanes, every lane stores its own sums as
 //         they lie (quarter or half lines per store instruction): the sweep's
 //         baseline for the two layouts, not used by the library.
 // ACCUM reads the target in BE_OUT's byte order, like k_reduce.
 // ---------------------------------------------------------------------------
-template <class H, bool BE_OUT, int START, int R, int BS, int MAP, bool VEC, int PF = 0, int E = 8, int XP = 1>
-__global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* __restrict__ bufs,
-                                                   const PartDesc* __restrict__ parts, int k, int tiles_per_part,
-                                                   int n_parts) {
+template <class S, bool BE_OUT, int START, int R, int BS, int MAP, bool VEC, int PF = 0, int E = 4, int XP = 1>
+__global__ __launch_bounds__(BS) void k_reduce_narrow(const typename S::elem* const* __restrict__ bufs,
+                                                      const PartDesc* __restrict__ parts, int k, int tiles_per_part,
+                                                      int n_parts) {
+  typedef typename S::elem T;
+  auto ldu = [](const T* p) { return S::unpack(S::template ldv<E>(p)); };   // what a lane keeps of a load
+  typedef decltype(ldu((const T*)nullptr)) V;
+  static_assert(E == 4 || (E == 8 && sizeof(T) == 2), "8 elements per lane: 16-bit sources only");
+  static_assert(XP == 1 || sizeof(T) == 2, "the no-exchange baseline: 16-bit sources only");
   constexpr int64_t kTile = (int64_t)BS * E * R;
-  constexpr int kPB = 8;           // peers in flight on the element-by-element path
-  constexpr int kPBV = 32 / E;     // ... and on the partial tile's vector steps: 64 B per lane in flight
-                                   // (8 peers of 16 B next to 8 f64 accumulators spill at 1024 lanes)
+  constexpr int kPB = 8;                               // peers in flight on the element-by-element path
+  constexpr int kPBV = S::template kPeersVec<E>;       // ... and on the partial tile's vector steps
   int q, t;
   map_block(MAP, gridDim.x, tiles_per_part, n_parts, q, t);
   if (q >= n_parts) return;
@@ -1929,25 +1674,22 @@ __global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* 
   const int64_t base = (int64_t)t * kTile;
   if (base >= L) return;
   unsigned long long* __restrict__ dst = parts[q].dst;
-  const unsigned short* const* __restrict__ pb = bufs + (size_t)q * k;
+  const T* const* __restrict__ pb = bufs + (size_t)q * k;
   const int tid = threadIdx.x;
   const int j0 = (START == kFirst) ? 1 : 0;
 
-  auto add = [](double (&a)[E], const HWords<E>& v) {
+  auto add = [](double (&a)[E], const V& v) {
 #pragma unroll
-    for (int c = 0; c < E / 2; ++c) {
-      a[2 * c] = a[2 * c] + H::lo(v.w[c]);
-      a[2 * c + 1] = a[2 * c + 1] + H::hi(v.w[c]);
-    }
+    for (int c = 0; c < E; ++c) a[c] = a[c] + S::template get<E>(v, c);
   };
   auto init = [&](double (&a)[E], int64_t o) {
     if constexpr (START == kZero) {
 #pragma unroll
       for (int c = 0; c < E; ++c) a[c] = 0.0;
     } else if constexpr (START == kFirst) {
-      const HWords<E> x = ldvh<E>(pb[0] + o);
+      const V x = ldu(pb[0] + o);
 #pragma unroll
-      for (int c = 0; c < E / 2; ++c) a[2 * c] = H::lo(x.w[c]), a[2 * c + 1] = H::hi(x.w[c]);
+      for (int c = 0; c < E; ++c) a[c] = S::template get<E>(x, c);
     } else {
 #pragma unroll
       for (int c = 0; c < E / 2; ++c) {
@@ -1964,18 +1706,18 @@ __global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* 
 #pragma unroll
     for (int r = 0; r < R; ++r) init(acc[r], o0 + (int64_t)r * BS * E);
     if constexpr (PF) {
-      HWords<E> v[R];
+      V v[R];
       if (j0 < k) {
-        const unsigned short* __restrict__ src = pb[j0] + o0;
+        const T* __restrict__ src = pb[j0] + o0;
 #pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = ldvh<E>(src + (int64_t)r * BS * E);
+        for (int r = 0; r < R; ++r) v[r] = ldu(src + (int64_t)r * BS * E);
       }
       for (int j = j0; j < k; ++j) {
-        HWords<E> nx[R];
+        V nx[R];
         if (j + 1 < k) {
-          const unsigned short* __restrict__ src = pb[j + 1] + o0;
+          const T* __restrict__ src = pb[j + 1] + o0;
 #pragma unroll
-          for (int r = 0; r < R; ++r) nx[r] = ldvh<E>(src + (int64_t)r * BS * E);
+          for (int r = 0; r < R; ++r) nx[r] = ldu(src + (int64_t)r * BS * E);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) add(acc[r], v[r]);
@@ -1984,10 +1726,10 @@ __global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* 
       }
     } else {
       for (int j = j0; j < k; ++j) {
-        const unsigned short* __restrict__ src = pb[j] + o0;
-        HWords<E> v[R];
+        const T* __restrict__ src = pb[j] + o0;
+        V v[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = ldvh<E>(src + (int64_t)r * BS * E);
+        for (int r = 0; r < R; ++r) v[r] = ldu(src + (int64_t)r * BS * E);
 #pragma unroll
         for (int r = 0; r < R; ++r) add(acc[r], v[r]);
       }
@@ -2000,14 +1742,20 @@ __global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* 
           __builtin_nontemporal_store(encode2<BE_OUT>(d2{acc[r][2 * c], acc[r][2 * c + 1]}),
                                       (gu2)(dst + o0 + (int64_t)r * BS * E + 2 * c));
     } else if constexpr (E == 4) {
-      // k_reduce_f32's store: the 8 lanes that own two adjacent lines swap their
-      // upper pair of sums with lane ^ 4, so each store instruction writes whole lines
+      // A lane's 4 sums are 32 B, so its own two 16-B stores would each cover
+      // half of every 128-B line the wave writes (measured: WRITE_SIZE 1.12x the
+      // algorithmic 8 L).  Instead the 8 lanes that own two adjacent lines
+      // (lanes 0-3 the first, 4-7 the second) swap their upper pair of sums
+      // with lane ^ 4: the first store instruction then writes the first line
+      // whole -- lanes 0-3 their own lower pairs, lanes 4-7 the upper pairs of
+      // lanes 0-3 -- and the second one the second line.  Values only move
+      // between lanes; every sum is unchanged.
       const bool hi = tid & 4;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int64_t o = o0 + (int64_t)r * BS * 4;
         const d2 own = d2{acc[r][0], acc[r][1]};
-        const d2 got = d2{__shfl_xor(acc[r][2], 4), __shfl_xor(acc[r][3], 4)};
+        const d2 got = d2{__shfl_xor(acc[r][2], 4), __shfl_xor(acc[r][3], 4)};   // elements o ^ 16 .. + 2, + 3
         __builtin_nontemporal_store(encode2<BE_OUT>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
         __builtin_nontemporal_store(encode2<BE_OUT>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
       }
@@ -2061,13 +1809,13 @@ __global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* 
       init(a, o);
       int jj = j0;
       for (; jj + kPBV <= k; jj += kPBV) {
-        HWords<E> v[kPBV];
+        V v[kPBV];
 #pragma unroll
-        for (int g = 0; g < kPBV; ++g) v[g] = ldvh<E>(pb[jj + g] + o);
+        for (int g = 0; g < kPBV; ++g) v[g] = ldu(pb[jj + g] + o);
 #pragma unroll
         for (int g = 0; g < kPBV; ++g) add(a, v[g]);
       }
-      for (; jj < k; ++jj) add(a, ldvh<E>(pb[jj] + o));
+      for (; jj < k; ++jj) add(a, ldu(pb[jj] + o));
 #pragma unroll
       for (int c = 0; c < E / 2; ++c)
         __builtin_nontemporal_store(encode2<BE_OUT>(d2{a[2 * c], a[2 * c + 1]}), (gu2)(dst + o + 2 * c));
@@ -2076,38 +1824,42 @@ __global__ __launch_bounds__(BS) void k_reduce_h16(const unsigned short* const* 
   for (int64_t e = sb + tid; e < end; e += BS) {
     double acc;
     if constexpr (START == kZero) acc = 0.0;
-    else if constexpr (START == kFirst) acc = H::one(ld2h(pb[0] + e));
+    else if constexpr (START == kFirst) acc = S::widen(S::ldraw(pb[0] + e));
     else acc = decode1<BE_OUT>(ld8(dst + e));
     int jj = j0;
     for (; jj + kPB <= k; jj += kPB) {
-      unsigned short v[kPB];
+      typename S::raw v[kPB];
 #pragma unroll
-      for (int g = 0; g < kPB; ++g) v[g] = ld2h(pb[jj + g] + e);
+      for (int g = 0; g < kPB; ++g) v[g] = S::ldraw(pb[jj + g] + e);
 #pragma unroll
-      for (int g = 0; g < kPB; ++g) acc = acc + H::one(v[g]);
+      for (int g = 0; g < kPB; ++g) acc = acc + S::widen(v[g]);
     }
-    for (; jj < k; ++jj) acc = acc + H::one(ld2h(pb[jj] + e));
+    for (; jj < k; ++jj) acc = acc + S::widen(S::ldraw(pb[jj] + e));
     st8(dst + e, BE_OUT ? f64_to_be(acc) : __builtin_bit_cast(unsigned long long, acc));
   }
 }
 
-// Shape of the 16-bit-source elementwise kernels when the partition's slice of
-// the flat vector and its destination are both 16-B aligned (VEC, decided by
-// the host per partition: flat + p*chunk is only 2-B aligned in general): a
-// block owns kEwTile consecutive elements, a lane one vector of 8.
-static_assert((int64_t)kBlock * 8 == kEwTile, "one elementwise tile size");
-
-// k_split over a 16-bit flat vector: OrganizeGradients (MODE 0) and
-// UpdateGradient's own accumulate (MODE 1, 2), the expressions of k_split on
-// v = (double)flat[lo + i].  The tile that holds the count slot goes element
-// by element.
-template <class H, bool BE_OUT, int MODE, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_split_h16(const unsigned short* __restrict__ flat, int64_t lo,
-                                                      int64_t ncopy, int64_t L, unsigned long long* __restrict__ dst) {
+// k_split over a flat vector of a narrow format: OrganizeGradients (MODE 0)
+// and UpdateGradient's own accumulate (MODE 1, 2), the expressions of k_split
+// on v = (double)flat[lo + i].  VEC (decided by the host per partition: flat +
+// p*chunk is only element-aligned in general): the partition's slice of the
+// flat vector and its destination are both 16-B aligned; a block then owns
+// kEwTile consecutive elements and a lane kEwTile / kBlock = 8 of them, as
+// 16-B loads of 16 / sizeof(elem) elements (2 vectors of 4 floats, vector k at
+// base + 4 * (k * kBlock + lane), or 1 vector of 8 16-bit elements).  The tile
+// that holds the count slot (1.0, what a widened count slot of 1 is) goes
+// element by element.
+template <class S, bool BE_OUT, int MODE, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_split_narrow(const typename S::elem* __restrict__ flat, int64_t lo,
+                                                         int64_t ncopy, int64_t L,
+                                                         unsigned long long* __restrict__ dst) {
   static_assert(MODE == 0 || !BE_OUT, "the folds write native doubles");
+  constexpr int EV = 16 / sizeof(typename S::elem);   // elements per load
+  constexpr int NV = kEwTile / kBlock / EV;           // loads per lane
+  static_assert((int64_t)kBlock * EV * NV == kEwTile, "one elementwise tile size");
   auto one = [&](int64_t i) {
     double v;
-    if (i < ncopy) v = H::one(ld2h(flat + lo + i));
+    if (i < ncopy) v = S::widen(S::ldraw(flat + lo + i));
     else if (i == ncopy) v = 1.0;
     else v = 0.0;
     if constexpr (MODE == 1) {
@@ -2122,26 +1874,35 @@ __global__ __launch_bounds__(kBlock) void k_split_h16(const unsigned short* __re
   if constexpr (VEC) {
     const int64_t base = (int64_t)blockIdx.x * kEwTile;
     if (base + kEwTile <= ncopy) {
-      const int64_t i = base + 8 * (int64_t)threadIdx.x;
-      const HWords<8> sv = ldvh<8>(flat + lo + i);
-      u2 dv[4];
-      if constexpr (MODE == 1) {
+      const typename S::elem* src = flat + lo;
+      typename S::template Vec<EV> sv[NV];
+      u2 dv[NV][EV / 2];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) dv[c] = *(gcu2)(dst + i + 2 * c);
+      for (int k = 0; k < NV; ++k) {
+        const int64_t i = base + EV * ((int64_t)k * kBlock + threadIdx.x);
+        sv[k] = S::template ldv<EV>(src + i);
+        if constexpr (MODE == 1) {
+#pragma unroll
+          for (int c = 0; c < EV / 2; ++c) dv[k][c] = *(gcu2)(dst + i + 2 * c);
+        }
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const d2 x = d2{H::lo(sv.w[c]), H::hi(sv.w[c])};
-        d2 o;
-        if constexpr (MODE == 1) {
-          const d2 a = __builtin_bit_cast(d2, dv[c]);
-          o = d2{a.x + x.x, a.y + x.y};
-        } else if constexpr (MODE == 2) {
-          o = d2{0.0 + x.x, 0.0 + x.y};
-        } else {
-          o = x;
+      for (int k = 0; k < NV; ++k) {
+        const int64_t i = base + EV * ((int64_t)k * kBlock + threadIdx.x);
+#pragma unroll
+        for (int c = 0; c < EV / 2; ++c) {
+          const d2 x = d2{S::template get<EV>(sv[k], 2 * c), S::template get<EV>(sv[k], 2 * c + 1)};
+          d2 o;
+          if constexpr (MODE == 1) {
+            const d2 a = __builtin_bit_cast(d2, dv[k][c]);
+            o = d2{a.x + x.x, a.y + x.y};
+          } else if constexpr (MODE == 2) {
+            o = d2{0.0 + x.x, 0.0 + x.y};
+          } else {
+            o = x;
+          }
+          *(gu2)(dst + i + 2 * c) = encode2<BE_OUT>(o);
         }
-        *(gu2)(dst + i + 2 * c) = encode2<BE_OUT>(o);
       }
       return;
     }
@@ -2153,33 +1914,43 @@ __global__ __launch_bounds__(kBlock) void k_split_h16(const unsigned short* __re
   }
 }
 
-// k_load_model over a 16-bit model (InitializeWeights from model.params()).
-template <class H>
-__global__ __launch_bounds__(kBlock) void k_load_model_h16(const unsigned short* __restrict__ flat, int64_t lo,
-                                                           int64_t ncopy, int64_t L, double* __restrict__ dst) {
+// k_load_model over a model of a narrow format (InitializeWeights from model.params()).
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_load_model_narrow(const typename S::elem* __restrict__ flat, int64_t lo,
+                                                              int64_t ncopy, int64_t L, double* __restrict__ dst) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= L) return;
-  dst[i] = (i < ncopy) ? H::one(ld2h(flat + lo + i)) : 0.0;
+  dst[i] = (i < ncopy) ? S::widen(S::ldraw(flat + lo + i)) : 0.0;
 }
 
 // ---------------------------------------------------------------------------
-// k_divide_h16: the GetPartitions divide narrowed to a 16-bit format:
-//   out[m] = narrow16((float)(cnt == 0.0 ? W[p][j] : W[p][j] / den))
-// k_divide's IEEE double division, rounded to float as k_divide_f32 does, then
-// that float rounded to the format (the two-step rule above).  Never a 16-bit
-// or f32 division, never a reciprocal.  Tiles are laid over the OUTPUT as in
-// k_divide_f32: block 0 writes the `head` values up to the first 128-B line of
-// this partition's output, then every lane stores 16 B = 8 values and a wave
-// whole lines; W is read with 8-B loads.
+// k_divide_narrow: the GetPartitions divide (k_divide) narrowed to a format:
+//   out[m] = narrow((float)(cnt == 0.0 ? W[p][j] : W[p][j] / den))
+// The quotient is k_divide's IEEE double division; it is rounded once to
+// float (ties to even; overflow to +-inf, subnormals kept, -0.0 stays -0.0),
+// and for a 16-bit format that float is rounded to the format (the two-step
+// rule above).  Never a division in the narrow format, never a reciprocal.
+// Tiles of kDivTile values are laid over the OUTPUT as in k_divide: block 0
+// writes the `head` values up to the first 128-B line of this partition's
+// output (p*chunk elements is arbitrary mod a line), then every lane stores
+// 16 B = 16 / sizeof(elem) values and a wave whole lines (64 x 16 B = 8
+// lines); W is read with 8-B loads (its alignment against the output is
+// arbitrary).
 // ---------------------------------------------------------------------------
-constexpr int kDivV16 = 1;
-constexpr int64_t kDivTile16 = (int64_t)kBlock * 8 * kDivV16;
-
-template <class H, bool SECURE, int BS = kBlock, int V = kDivV16>
-__global__ __launch_bounds__(BS) void k_divide_h16(const DivDesc* __restrict__ parts, const double* __restrict__ arena,
-                                                   unsigned short* __restrict__ out, int tiles_per_part) {
-  constexpr int64_t kTile = (int64_t)BS * 8 * V;
-  static_assert(BS % 64 == 0, "whole waves");
+template <class S, bool SECURE>
+__global__ __launch_bounds__(kBlock) void k_divide_narrow(const DivDesc* __restrict__ parts,
+                                                          const double* __restrict__ arena,
+                                                          typename S::elem* __restrict__ out, int tiles_per_part) {
+  typedef typename S::elem T;
+  constexpr int EV = 16 / sizeof(T);                   // values per store
+  constexpr int PW = 4 / sizeof(T);                    // values per 32-bit word
+  constexpr int V = kDivTile / ((int64_t)kBlock * EV); // stores per lane
+  constexpr int LINE = 128 / sizeof(T);                // values per 128-B line
+  // kDivTile is the f64 divide's tile, tuned for k_divide (kDivV).  The shape below (V stores per lane) was
+  // measured at 2048 values: a retuned kDivV must not change it unnoticed.
+  static_assert(kDivTile == 2048, "the narrow divide's tile is 2048 values");
+  static_assert((int64_t)kBlock * EV * V == kDivTile, "one divide tile size for every element size");
+  static_assert(kBlock % 64 == 0, "whole waves");
   const int q = blockIdx.x / tiles_per_part;
   const int t = blockIdx.x - q * tiles_per_part;
   const DivDesc d = parts[q];
@@ -2187,37 +1958,42 @@ __global__ __launch_bounds__(BS) void k_divide_h16(const DivDesc* __restrict__ p
   const double* w = arena + d.w_off;
   const double cnt = w[d.len - 1];
   const double den = SECURE ? 1e12 * cnt : cnt;   // IPLS.java:1167
-  auto f = [&](double x) -> unsigned { return H::narrow((float)((cnt == 0.0) ? x : x / den)); };
-  unsigned short* o = out + d.out_off;
-  const int64_t to_line = (64 - (int64_t)(((uintptr_t)o >> 1) & 63)) & 63;   // values to a 128-B boundary
+  auto f = [&](double x) -> unsigned { return S::narrow((float)((cnt == 0.0) ? x : x / den)); };
+  T* o = out + d.out_off;
+  const int64_t to_line = (LINE - (int64_t)(((uintptr_t)o / sizeof(T)) & (LINE - 1))) & (LINE - 1);
   const int64_t head = to_line < n ? to_line : n;
-  if (t == 0 && threadIdx.x < head) *(gu16)(o + threadIdx.x) = (unsigned short)f(w[threadIdx.x]);
-  const int64_t base = (int64_t)t * kTile + head;
+  if (t == 0 && threadIdx.x < head) S::put(o + threadIdx.x, f(w[threadIdx.x]));
+  const int64_t base = (int64_t)t * kDivTile + head;
   if (base >= n) return;
-  if (base + kTile <= n) {
-    // wave (threadIdx.x / 64) owns [base + wave * 512 * V, + 512 * V)
-    const int64_t wave_base = base + (int64_t)(threadIdx.x >> 6) * 512 * V + 8 * (threadIdx.x & 63);
-    double x[V][8];
+  if (base + kDivTile <= n) {
+    // wave (threadIdx.x / 64) owns [base + wave * 64 * EV * V, + 64 * EV * V)
+    const int64_t wave_base = base + (int64_t)(threadIdx.x >> 6) * 64 * EV * V + EV * (threadIdx.x & 63);
+    double x[V][EV];
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      const int64_t i = wave_base + (int64_t)v * 512;
+      const int64_t i = wave_base + (int64_t)v * 64 * EV;
 #pragma unroll
-      for (int c = 0; c < 8; ++c)
-        x[v][c] = __builtin_nontemporal_load((const __attribute__((address_space(1))) double*)(w + i + c));
+      for (int c = 0; c < EV; ++c)
+        x[v][c] = __builtin_nontemporal_load((const IPLS_GLOBAL double*)(w + i + c));
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      const int64_t i = wave_base + (int64_t)v * 512;
+      const int64_t i = wave_base + (int64_t)v * 64 * EV;
+      // The four words are spelled out: with a loop over them inside this one, which has a single
+      // trip for 16-bit elements, hipcc hoists the store out of it and drops its non-temporal hint
+      // (seen in the assembly; GetPartitions to bfloat16 then ran a few per cent slower, runs not kept).
+      const double* xv = x[v];
       u4w y;
-      y.x = f(x[v][0]) | (f(x[v][1]) << 16);
-      y.y = f(x[v][2]) | (f(x[v][3]) << 16);
-      y.z = f(x[v][4]) | (f(x[v][5]) << 16);
-      y.w = f(x[v][6]) | (f(x[v][7]) << 16);
-      __builtin_nontemporal_store(y, (gu4w)(o + i));
+      if constexpr (PW == 2)
+        y = u4w{f(xv[0]) | (f(xv[1]) << 16), f(xv[2]) | (f(xv[3]) << 16), f(xv[4]) | (f(xv[5]) << 16),
+                f(xv[6]) | (f(xv[7]) << 16)};
+      else
+        y = u4w{f(xv[0]), f(xv[1]), f(xv[2]), f(xv[3])};
+      __builtin_nontemporal_store(y, (IPLS_GLOBAL u4w*)(o + i));
     }
     return;
   }
-  for (int64_t i = base + threadIdx.x; i < n; i += BS) *(gu16)(o + i) = (unsigned short)f(w[i]);
+  for (int64_t i = base + threadIdx.x; i < n; i += kBlock) S::put(o + i, f(w[i]));
 }
 
 }  // namespace ipls

@@ -9,8 +9,8 @@ References: Model.java:423 (toDoubleVector -> UpdateGradient, IPLS.java:1737-
 1743; OrganizeGradients 1018-1040), Model.java:388-390 (GetPartitions 1140-1174
 narrowed), Updater.java:115-117 (the arrival fold), IPLS.java:1248-1274.
 
-Shapes: T is k_reduce_f32's tile (1024 lanes x 4 floats x 2 vectors; one shape
-class); L in {1, 2, 3, 4, 5, 7, 9, T-1, T, T+1, 2T+3}, P in {3, 5}, k in
+Shapes: T is the tile of k_reduce_narrow over floats (1024 lanes x 4 floats x
+2 vectors; one shape class); L in {1, 2, 3, 4, 5, 7, 9, T-1, T, T+1, 2T+3}, P in {3, 5}, k in
 {1, 2, 3, 8, 9, 33}; the reference geometry M = 30,011 with 3 partitions, also
 on a two-shard handle; ETHModel (443,610 values) once.
 """
@@ -24,7 +24,7 @@ from conftest import assert_bits_equal
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-T = 8192             # elements per tile of k_reduce_f32: block 1024 x 4 x vectors 2
+T = 8192             # elements per tile of k_reduce_narrow over floats: block 1024 x 4 x vectors 2
 KS = (1, 2, 3, 8, 9, 33)
 LS = (1, 2, 3, 4, 5, 7, 9, T - 1, T, T + 1, 2 * T + 3)
 INVAL = -1
@@ -196,6 +196,51 @@ def test_reduce_batch_f32_misaligned(ipls, O, off):
             assert li["kernel"] == ipls.KERNEL_REDUCE_F32 and li["seqf"] == 0
             for q in range(P):
                 assert_bits_equal(agg.read(q), O.reduce(_widen(x[q * k:(q + 1) * k]), L, mode), f"off={off} mode={mode}")
+
+
+_TILE = {}
+
+
+def _tile(ipls):
+    """(T, block) of the fold over floats, read from the launch record."""
+    if not _TILE:
+        keep, rows = _dev_rows(np.ones((1, 9), dtype=np.float32))
+        with ipls.Aggregator(n_partitions=1, bucket_len=9) as agg:
+            agg.reduce_batch(0, [_db(ipls, rows)])
+            li = agg.last_launch()
+        assert li["kernel"] == ipls.KERNEL_REDUCE_F32
+        _TILE["T"], _TILE["block"] = li["block"] * 4 * li["vectors"], li["block"]
+        assert _TILE["T"] <= 32768
+    return _TILE["T"], _TILE["block"]
+
+
+@pytest.mark.parametrize("k", (1, 9))
+@pytest.mark.parametrize("lname", ("7", "T+1", "2T+3", "T+4b+1"))
+def test_reduce_batch_out_accum_big_endian_f32(ipls, O, lname, k):
+    """ACCUM onto big-endian caller destinations that hold random doubles: three
+    partitions in one launch, bit-exact against the oracle's ACCUM fold.  T + 4b + 1
+    (b lanes) gives the partial tile one vector step of 4 elements per lane."""
+    Tl, b = _tile(ipls)
+    L, P = {"7": 7, "T+1": Tl + 1, "2T+3": 2 * Tl + 3, "T+4b+1": Tl + 4 * b + 1}[lname], 3
+    rng = np.random.default_rng(900 + 10 * L + k)
+    x = _f32_buckets(rng, P * k, L).reshape(P, k, L)
+    keep, rows = _dev_rows(x.reshape(P * k, L))
+    bufs = _db(ipls, rows)
+    tab = [[bufs[q * k + j] for j in range(k)] for q in range(P)]
+    prior = rng.standard_normal((P, L))
+    Lp = (L + 1) // 2 * 2
+    d = torch.zeros((P, Lp), dtype=torch.int64, device="cuda")
+    d[:, :L] = torch.from_numpy(prior.astype(">f8").view(np.int64).copy()).cuda()
+    torch.cuda.synchronize()
+    with ipls.Aggregator(n_partitions=P, bucket_len=L) as agg:
+        agg.reduce_batch_out(0, tab, [ipls.DeviceBuffer(d[q].data_ptr(), L, True) for q in range(P)],
+                             start_mode=ipls.START_ACCUM, big_endian_out=True)
+        li = agg.last_launch()
+        assert li["kernel"] == ipls.KERNEL_REDUCE_F32 and li["seqf"] == 1
+        agg.sync()
+    got = d.cpu().numpy().view(">f8").astype(np.float64)
+    for q in range(P):
+        assert_bits_equal(got[q, :L], O.reduce(_widen(x[q]), L, O.START_ACCUM, prior[q]), f"L={L} k={k} p={q}")
 
 
 # --------------------------------------------------------------------------

@@ -105,7 +105,7 @@ _TILE = {}
 
 
 def _tile(ipls):
-    """(T, block) of k_reduce_h16, read from the launch record."""
+    """(T, block) of k_reduce_narrow over 16-bit buckets, read from the launch record."""
     if not _TILE:
         bits = np.full((1, 9), R.one("half"), dtype=np.uint16)
         keep, rows = _dev_rows(bits, "half")
@@ -230,6 +230,39 @@ def test_reduce_batch_h16(ipls, O, fmt, lname):
             agg.Update(acc0, 0)
             agg.reduce_batch(0, tab, start_mode=ipls.START_ACCUM)
             assert_bits_equal(agg.read(0), O.reduce(wide[:k], L, O.START_ACCUM, 0.0 + acc0), f"{fmt} L={L} k={k} AGG")
+
+
+@pytest.mark.parametrize("k", (1, 9))
+@pytest.mark.parametrize("lname", ("7", "T+1", "2T+3", "T+4b+1"))
+@pytest.mark.parametrize("fmt", FMTS)
+def test_reduce_batch_out_accum_big_endian(ipls, O, fmt, lname, k):
+    """ACCUM onto big-endian caller destinations that hold random doubles: three
+    partitions in one launch, bit-exact against the oracle's ACCUM fold.  T + 4b + 1
+    (b lanes) gives the partial tile one vector step of 4 elements per lane."""
+    T, b = _tile(ipls)
+    L, P = {"7": 7, "T+1": T + 1, "2T+3": 2 * T + 3, "T+4b+1": T + 4 * b + 1}[lname], 3
+    rng = np.random.default_rng(900 + 10 * L + k + len(fmt))
+    xs = [_buckets(ipls, rng, k, L, fmt) for _ in range(P)]
+    keeps, tab = [], []
+    for x in xs:
+        keep, rows = _dev_rows(x, fmt)
+        keeps.append(keep)
+        tab.append(_db(ipls, rows))
+    prior = rng.standard_normal((P, L))
+    Lp = (L + 1) // 2 * 2
+    d = torch.zeros((P, Lp), dtype=torch.int64, device="cuda")
+    d[:, :L] = torch.from_numpy(prior.astype(">f8").view(np.int64).copy()).cuda()
+    torch.cuda.synchronize()
+    with ipls.Aggregator(n_partitions=P, bucket_len=L) as agg:
+        agg.reduce_batch_out(0, tab, [ipls.DeviceBuffer(d[q].data_ptr(), L, True) for q in range(P)],
+                             start_mode=ipls.START_ACCUM, big_endian_out=True)
+        li = agg.last_launch()
+        assert li["kernel"] == ipls.KERNEL_REDUCE_H16 and li["seqf"] == 1
+        agg.sync()
+    got = d.cpu().numpy().view(">f8").astype(np.float64)
+    for q in range(P):
+        assert_bits_equal(got[q, :L], O.reduce(_widen(xs[q], fmt), L, O.START_ACCUM, prior[q]),
+                          f"{fmt} L={L} k={k} p={q}")
 
 
 @pytest.mark.parametrize("fmt", FMTS)

@@ -6,7 +6,7 @@ of float buckets) and on a 64 Mi-value model:
  (a) widen first: every float bucket copied into a double bucket by torch
      (what ``bucket.double()`` does, into preallocated memory), then
      reduce_batch on the doubles -- both parts timed;
- (b) reduce_batch on the float buckets (k_reduce_f32); every partition's
+ (b) reduce_batch on the float buckets (k_reduce_narrow<FmtF32>); every partition's
      checksum must equal (a)'s before anything is reported;
  (c) UpdateGradient and GetPartitions at M = 64 Mi: ``.double()`` + DEV_F64 and
      DEV_F64 + ``.float()`` against the f32 kinds.
@@ -17,7 +17,7 @@ Fractions are of 8 TB/s over algorithmic bytes: (4K + 8) L P for (b),
 (8K + 8) L P for the f64 fold.
 Usage: f32_fold_probe.py [OUT.json] [REPS]
        f32_fold_probe.py --fold-only N    N launches of (b) and nothing else: the workload of a
-                                          rocprofv3 --pmc pass (tools/pmc_traffic.py ... k_reduce_f32)"""
+                                          rocprofv3 --pmc pass (tools/pmc_traffic.py ... k_reduce_narrow)"""
 import json
 import sys
 from pathlib import Path

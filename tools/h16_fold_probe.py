@@ -4,8 +4,8 @@ in one process, at config C's geometry (16 partitions x 4,194,305 x 32 peers;
 4.3 GB of 16-bit buckets) and on a 64 Mi-value model, for each of the two
 formats (IEEE binary16 "half", bfloat16 "bf16"):
 
- (h) reduce_batch on the 16-bit buckets (k_reduce_h16);
- (f) reduce_batch on the same values widened to float (exact): k_reduce_f32;
+ (h) reduce_batch on the 16-bit buckets (k_reduce_narrow<FmtF16 | FmtBF16>);
+ (f) reduce_batch on the same values widened to float (exact): k_reduce_narrow<FmtF32>;
  (w) torch ``.float()`` of every bucket (into preallocated memory), then (f) --
      the only route a user had: both parts timed;
  (d) reduce_batch on the same values as doubles: the f64 fold;

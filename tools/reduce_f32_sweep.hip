@@ -1,9 +1,9 @@
-// reduce_f32_sweep.hip -- dev tool: time k_reduce_f32 shapes on one MI355X.
+// reduce_f32_sweep.hip -- dev tool: time k_reduce_narrow shapes over float buckets on one MI355X.
 //
 // Usage: reduce_f32_sweep P L K REPS
 // Allocates P*K float buckets of L elements (16-B aligned), fills them with
 // (2u-1)*1e-2 from splitmix64 and 1.0f in the count slot, then times every
-// (lanes, vectors per lane, next-peer prefetch) variant of k_reduce_f32 REPS times,
+// (lanes, vectors per lane, next-peer prefetch) variant of k_reduce_narrow<FmtF32> REPS times,
 // interleaved round-robin in one process, START_ZERO into native doubles.
 // Reports the median and minimum kernel time (hipEvents, one launch per
 // sample after a warm-up launch) and the fraction of 8 TB/s over the
@@ -80,10 +80,10 @@ int main(int argc, char** argv) {
   vs.push_back(Variant{"bs" #BS "_r" #R "_pf" #PF, (int64_t)BS * 4 * R, [=](int64_t tpp, bool partial) {             \
                          const dim3 g((unsigned)(tpp * P));                                                 \
                          if (partial)                                                                       \
-                           hipLaunchKernelGGL((k_reduce_f32<false, kZero, R, BS, 3, true, PF>), g, dim3(BS), 0, 0, \
+                           hipLaunchKernelGGL((k_reduce_narrow<FmtF32, false, kZero, R, BS, 3, true, PF>), g, dim3(BS), 0, 0, \
                                               (const float* const*)dbufs, dparts, K, (int)tpp, P);          \
                          else                                                                               \
-                           hipLaunchKernelGGL((k_reduce_f32<false, kZero, R, BS, 0, true, PF>), g, dim3(BS), 0, 0, \
+                           hipLaunchKernelGGL((k_reduce_narrow<FmtF32, false, kZero, R, BS, 0, true, PF>), g, dim3(BS), 0, 0, \
                                               (const float* const*)dbufs, dparts, K, (int)tpp, P);          \
                        }, {}})
   VAR(256, 2, 0);

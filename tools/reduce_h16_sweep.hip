@@ -1,12 +1,12 @@
-// reduce_h16_sweep.hip -- dev tool: time k_reduce_h16 shapes on one MI355X.
+// reduce_h16_sweep.hip -- dev tool: time k_reduce_narrow shapes over 16-bit buckets on one MI355X.
 //
 // Usage: reduce_h16_sweep P L K REPS [half|bf16]
 // Allocates P*K 16-bit buckets of L elements (16-B aligned), fills them with
 // (2u-1)*1e-2 from splitmix64 narrowed to the format and 1.0 in the count
 // slot, then times every (layout, lanes, vectors per lane, next-peer prefetch)
-// variant of k_reduce_h16 REPS times, interleaved round-robin in one process,
+// variant of k_reduce_narrow REPS times, interleaved round-robin in one process,
 // START_ZERO into native doubles.  Layout A: 8-B loads, 4 elements per lane,
-// k_reduce_f32's lane^4 swap; layout B: 16-B loads, 8 elements per lane, the
+// the lane^4 swap of the float fold; layout B: 16-B loads, 8 elements per lane, the
 // pair transpose across 8 lanes; Aplain / Bplain: the same without any exchange
 // between lanes (half- and quarter-line stores).  Sum slots are 128-B aligned
 // like the library's arena.  Reports the median and minimum kernel time
@@ -86,10 +86,10 @@ int run(int P, int64_t L, int K, int reps, const char* fmt) {
   vs.push_back(Variant{#LAY "_bs" #BS "_r" #R "_pf" #PF, (int64_t)BS * E * R, [=](int64_t tpp, bool partial) {     \
                          const dim3 g((unsigned)(tpp * P));                                                        \
                          if (partial)                                                                              \
-                           hipLaunchKernelGGL((k_reduce_h16<H, false, kZero, R, BS, 3, true, PF, E, XP>), g, dim3(BS), \
+                           hipLaunchKernelGGL((k_reduce_narrow<H, false, kZero, R, BS, 3, true, PF, E, XP>), g, dim3(BS), \
                                               0, 0, (const unsigned short* const*)dbufs, dparts, K, (int)tpp, P);  \
                          else                                                                                      \
-                           hipLaunchKernelGGL((k_reduce_h16<H, false, kZero, R, BS, 0, true, PF, E, XP>), g, dim3(BS), \
+                           hipLaunchKernelGGL((k_reduce_narrow<H, false, kZero, R, BS, 0, true, PF, E, XP>), g, dim3(BS), \
                                               0, 0, (const unsigned short* const*)dbufs, dparts, K, (int)tpp, P);  \
                        }, {}})
   VAR(A, 4, 256, 4, 1);
