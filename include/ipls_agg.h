@@ -516,10 +516,21 @@ int ipls_agg_finalize_chunked(ipls_agg *h, int p, int sum_kind, int64_t chunk, i
  *   avg_out  = W[p][j] / W[p][L_p-1]            GetPartitions divide (IPLS.java:1159-1174)
  * AGG is never stored: its final value only feeds W.  Results are bit-identical
  * to reduce_batch(ACCUM) + finalize + get_partitions.  bufs: n_parts*k device
- * buckets (DEV_F64/DEV_BE, k may be 0).  avg_out (or NULL) receives the
- * averaged values of the partitions, partition p at flat offset
- * partition_offset(p) - partition_offset(p_first) -- for all partitions the
- * GetPartitions model; avg_kind DEV_F64 or HOST_F64. */
+ * buckets (DEV_F64/DEV_BE, or the trainer kinds DEV_F32/DEV_F16/DEV_BF16; k
+ * may be 0).  avg_out (or NULL) receives the averaged values of the
+ * partitions, partition p at flat offset partition_offset(p) -
+ * partition_offset(p_first) -- for all partitions the GetPartitions model;
+ * avg_kind DEV_F64 or HOST_F64, or a DEV/HOST F32, F16 or BF16 kind (the
+ * narrowing rules of those kinds).
+ * What runs fused (one launch after a one-wave-per-partition count pre-pass),
+ * every bucket 16-B aligned:
+ *   DEV_F64 / DEV_BE buckets, avg_out NULL or DEV_F64 / HOST_F64   (k_round)
+ *   DEV_F32 / DEV_F16 / DEV_BF16 buckets, avg_out NULL or any of the six
+ *   trainer kinds, bucket and average formats free to differ   (k_round_narrow)
+ * What takes the three steps (the fold into AGG, AggregatePartition, the
+ * divide) inside the call, with the same bits: a bucket off a 16-B boundary;
+ * trainer-format buckets with F64 averages; F64 / BE buckets with
+ * trainer-format averages.  A HOST avg_kind adds one device-to-host copy. */
 int ipls_agg_aggregate_round(ipls_agg *h, int p_first, int n_parts,
                              const void *const *bufs, int k, int src_kind,
                              void *avg_out, int avg_kind);
@@ -689,6 +700,9 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
 #define IPLS_KERNEL_REDUCE_H16    6  /* k_reduce_narrow over DEV_F16 / DEV_BF16 buckets; a tile is block x 4 x
                                         vectors elements; shape 0; seqf 1 when every operand was 16-B
                                         aligned (vector path), 0 for the element-by-element form */
+#define IPLS_KERNEL_ROUND_F32     7  /* k_round_narrow (fused) over DEV_F32 buckets; a tile is block x 4 x
+                                        vectors elements; shape 0; seqf 1; map 3 (partial tiles first) or 0 */
+#define IPLS_KERNEL_ROUND_H16     8  /* k_round_narrow (fused) over DEV_F16 / DEV_BF16 buckets; as above */
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2
 #define IPLS_SHAPE_SMALL  3

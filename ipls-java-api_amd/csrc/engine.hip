@@ -914,6 +914,35 @@ ipls_launch_info launch_reduce_narrow(bool be_out, int start, bool vec, int64_t 
   return launch_info(K.kernel, 0, K.bs, K.r, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false, be_out, start);
 }
 
+// ---- kernel dispatch: k_round_narrow (the fused round over DEV_F32 / DEV_F16 / DEV_BF16 buckets) ----
+// The fold's shape (narrow_shape<S>: 1024 lanes x 2 vectors of floats, x 4 of
+// 16-bit elements, the next peer prefetched), every operand 16-B aligned; the
+// count pre-pass first, as for k_round.  A: the averages' format (S when the
+// round writes none).  ZERO or ACCUM start; partial last tiles first (map 3).
+template <class S, class A>
+ipls_launch_info launch_round_narrow(int start, int secure, int64_t maxL, int n_parts, hipStream_t st,
+                                     const typename S::elem* const* bufs, const PartDesc* parts, int k,
+                                     double* cnts) {
+  constexpr NarrowShape K = narrow_shape<S>();
+  const int64_t tile = (int64_t)K.bs * K.e * K.r;
+  const int64_t tpp = (maxL + tile - 1) / tile;
+  const bool partial = tpp > 1 && maxL % tile != 0;
+  const int map = partial ? 3 : 0;
+  const dim3 grid((unsigned)(tpp * n_parts));
+#define RNF(ST)                                                                                              \
+  do {                                                                                                       \
+    hipLaunchKernelGGL((k_round_counts_narrow<S, ST>), dim3(n_parts), dim3(64), 0, st, bufs, parts, k,       \
+                       n_parts, cnts);                                                                       \
+    hipLaunchKernelGGL((k_round_narrow<S, A, ST, K.r, K.bs, K.pf>), grid, dim3(K.bs), 0, st, bufs, parts, k, \
+                       (int)tpp, n_parts, map, secure, (const double*)cnts);                                 \
+  } while (0)
+  if (start == kZero) RNF(kZero);
+  else RNF(kAccum);
+#undef RNF
+  return launch_info(sizeof(typename S::elem) == 4 ? IPLS_KERNEL_ROUND_F32 : IPLS_KERNEL_ROUND_H16, 0, K.bs, K.r, 1,
+                     map, grid.x, false, false, start);
+}
+
 // Core of accumulate / reduce_batch: all pointers device-resident.  The
 // destination is the handle's `target` accumulators, or -- when ext_dst is
 // given -- one caller buffer per partition (doubles or, be_out, BE bytes).
@@ -922,6 +951,7 @@ ipls_launch_info launch_reduce_narrow(bool be_out, int start, bool vec, int64_t 
 // REP end logically zero.  Callers guarantee 16-B aligned buckets.
 struct FinOut {
   unsigned long long* avg;   // averages of p_first.. at flat_off[p] - flat_off[p_first], or null
+  Fmt fmt = kFmtF64;         // their format: doubles, or with trainer-format buckets a trainer format
 };
 
 // host_src: the bucket is pinned host memory read over PCIe (zero copy); the
@@ -931,7 +961,8 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
                int start_mode, int target, void* const* ext_dst = nullptr, bool be_out = false,
                const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr) {
   // fmt_in: what the buckets hold.  The trainer formats (floats, halves,
-  // bfloat16s) are aligned to their element size and never come with fin.
+  // bfloat16s) are aligned to their element size; with fin they take
+  // k_round_narrow, the averages (if any) in a trainer format too.
   const bool be_in = fmt_in == kFmtBE, tr_in = fmt_trainer(fmt_in);
   // lens: lengths of caller destinations that are not this engine's
   // partitions (ext_dst only, e.g. a replica slot's partial sums)
@@ -1015,7 +1046,9 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
     if (fin) {
       pd[q].init = (const unsigned long long*)(h->arena + h->agg_off[p]);
       if (!h->rep_zero[p]) pd[q].rep = (const unsigned long long*)(h->arena + h->rep_off[p]);
-      if (fin->avg) pd[q].avg = fin->avg + (h->flat_off[p] - h->flat_off[p_first]);
+      if (fin->avg)   // a byte pointer: the averages' elements are doubles or of a trainer format
+        pd[q].avg = (unsigned long long*)((char*)fin->avg +
+                                          (h->flat_off[p] - h->flat_off[p_first]) * (int64_t)fmt_size(fin->fmt));
     }
     if (!pd[q].dst) return fail(h, IPLS_E_INVAL, "destination %d is NULL", q);
     if ((uintptr_t)pd[q].dst & 7) return fail(h, IPLS_E_INVAL, "destination %d not 8-byte aligned", q);
@@ -1028,8 +1061,19 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   const PartDesc* dparts = (const PartDesc*)dtab;
   auto dbufs = (const unsigned long long* const*)((char*)dtab + desc_bytes);
   if (fin) {
-    if (!aligned16 || tr_in) return fail(h, IPLS_E_INVAL, "fused round needs 16-B aligned F64/BE buckets");
-    h->last_launch = launch_reduce_fin(be_in, start, h->secure, maxL, n_parts, h->stream, dbufs, dparts, k, h->d_cnt);
+    if (!aligned16 || (fin->avg && tr_in != fmt_trainer(fin->fmt)))
+      return fail(h, IPLS_E_INVAL, "fused round needs 16-B aligned buckets and averages of the buckets' family");
+    if (tr_in) {
+      h->last_launch = with_narrow(fmt_in, [&](auto s) {
+        typedef decltype(s) S;
+        return with_narrow(fin->avg ? fin->fmt : fmt_in, [&](auto a) {
+          return launch_round_narrow<S, decltype(a)>(kstart(start), h->secure, maxL, n_parts, h->stream,
+                                                     (const typename S::elem* const*)dbufs, dparts, k, h->d_cnt);
+        });
+      });
+    } else {
+      h->last_launch = launch_reduce_fin(be_in, start, h->secure, maxL, n_parts, h->stream, dbufs, dparts, k, h->d_cnt);
+    }
     HIP_TRY(h, hipGetLastError());
     for (int q = p_first; q < p_first + n_parts; ++q) h->agg_zero[q] = h->rep_zero[q] = 1;
     return IPLS_OK;
@@ -2798,14 +2842,16 @@ int dev_aggregate_round(ipls_dev* h, int p_first, int n_parts, const void* const
   }
   bool aligned16 = true;
   for (int64_t i = 0; i < (int64_t)n_parts * k; ++i) aligned16 = aligned16 && !((uintptr_t)bufs[i] & 15);
-  if (aligned16 && !tr_in && !tr_avg) {
-    FinOut fo{d_avg};
+  // fused: doubles in, doubles out (k_round); a trainer format in, none or a trainer format out (k_round_narrow)
+  if (aligned16 && (tr_in ? (!avg_out || tr_avg) : !tr_avg)) {
+    FinOut fo{d_avg, fmt_avg};
     if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, fmt_in, IPLS_START_ACCUM, IPLS_TGT_AGG,
                             nullptr, false, &fo))
       return rc;
   } else {
     // 8-B aligned buckets (frames at odd offsets): the same three steps unfused
-    // trainer-format buckets or averages: the widening fold / the narrowing
+    // trainer-format buckets off a 16-B boundary or with F64 averages, F64 / BE
+    // buckets with trainer-format averages: the widening fold / the narrowing
     // divide take the place of the fused kernel's halves (bit-identical by definition)
     if (int rc = reduce_dev(h, p_first, n_parts, bufs, k, fmt_in, IPLS_START_ACCUM, IPLS_TGT_AGG)) return rc;
     if (int rc = finalize_range(h, p_first, n_parts)) return rc;

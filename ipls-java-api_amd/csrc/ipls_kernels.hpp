@@ -1996,4 +1996,264 @@ __global__ __launch_bounds__(kBlock) void k_divide_narrow(const DivDesc* __restr
   for (int64_t i = base + threadIdx.x; i < n; i += kBlock) S::put(o + i, f(w[i]));
 }
 
+// ---------------------------------------------------------------------------
+// k_round_narrow: the fused round (k_round) for the trainer formats -- buckets
+// of format S in, W as native doubles and the averages in format A out, in one
+// pass: AGG is never stored.  The body is k_reduce_narrow's VEC path (E = 4
+// elements per lane per vector, one non-temporal load per peer per vector, PF:
+// the next peer's loads issued before this peer's adds), followed by
+// reduce_tiles<FIN>'s epilogue restated for four f64 accumulators per vector.
+// Per element e holding the fold value a:
+//   w      = a + (rep ? REP[e] : 0.0)          AggregatePartition (IPLS.java:1256); the + 0.0 is kept
+//   W[e]   = w                                 native doubles, the lane ^ 4 swap of k_reduce_narrow
+//   avg[e] = A::narrow((float)(cnt == 0.0 ? w : w / den))   for e < L - 1: k_divide_narrow's expression
+// (an IEEE double division, one rounding to float, then the format's own).
+// The host guarantees 16-B aligned buckets; AGG, REP and W are arena slots.
+// Averages: partition p's start at an arbitrary element of the output.  With
+// m = (address of parts[q].avg / sizeof(A::elem)) mod 4, uniform per block:
+//   m == 0: a lane stores its own four values (16 B of floats, 8 B of 16-bit);
+//   m != 0: a lane stores the aligned group made of its own last m values and
+//           lane t+1's first 4 - m (__shfl_down, as k_round does at 8 mod 16);
+//           the wave's first 4 - m and last m values go element by element.
+// Either way one store instruction of a wave writes one contiguous run (1 KiB
+// of floats, 512 B of 16-bit values) of which only the two ends share a line.
+// The last element of a full tile may be the count slot L - 1 (L a multiple of
+// the tile): it gets W but no average.  The partial last tile goes through
+// k_reduce_narrow's 4*BS-element vector steps and scalar remainder, every
+// element finishing through fin1.
+//   map : 0 partition-major, 3 partial tiles first (map_block); a runtime
+//         argument: 3 x 3 x 2 instantiations instead of 36.
+// ---------------------------------------------------------------------------
+template <class A>
+__device__ __forceinline__ void st_avg1(typename A::elem* p, unsigned b) {   // one average, as a global store
+  if constexpr (sizeof(typename A::elem) == 4) *(IPLS_GLOBAL unsigned*)p = b;
+  else *(IPLS_GLOBAL unsigned short*)p = (unsigned short)b;
+}
+template <class A>
+__device__ __forceinline__ void st_avg4(typename A::elem* p, unsigned g0, unsigned g1, unsigned g2, unsigned g3) {
+  if constexpr (sizeof(typename A::elem) == 4) {
+    __builtin_nontemporal_store(u4w{g0, g1, g2, g3}, (IPLS_GLOBAL u4w*)p);
+  } else {
+    typedef unsigned u2w __attribute__((ext_vector_type(2)));
+    __builtin_nontemporal_store(u2w{g0 | (g1 << 16), g2 | (g3 << 16)}, (IPLS_GLOBAL u2w*)p);
+  }
+}
+
+template <class S, class A, int START, int R, int BS, int PF>
+__global__ __launch_bounds__(BS) void k_round_narrow(const typename S::elem* const* __restrict__ bufs,
+                                                     const PartDesc* __restrict__ parts, int k, int tiles_per_part,
+                                                     int n_parts, int map, int secure,
+                                                     const double* __restrict__ cnts) {
+  typedef typename S::elem T;
+  typedef typename A::elem O;
+  constexpr int E = 4;
+  static_assert(START == kZero || START == kAccum, "AGG is never FIRST-started");
+  auto ldu = [](const T* p) { return S::unpack(S::template ldv<E>(p)); };
+  typedef decltype(ldu((const T*)nullptr)) V;
+  constexpr int64_t kTile = (int64_t)BS * E * R;
+  constexpr int kPB = 8;
+  constexpr int kPBV = S::template kPeersVec<E>;
+  int q, t;
+  map_block(map, gridDim.x, tiles_per_part, n_parts, q, t);
+  if (q >= n_parts) return;
+  const int64_t L = parts[q].len;
+  const int64_t base = (int64_t)t * kTile;
+  if (base >= L) return;
+  unsigned long long* __restrict__ dst = parts[q].dst;           // W
+  const unsigned long long* __restrict__ agg = parts[q].init;    // ACCUM source
+  const unsigned long long* __restrict__ rep = parts[q].rep;
+  O* __restrict__ avg = (O*)parts[q].avg;
+  const T* const* __restrict__ pb = bufs + (size_t)q * k;
+  const int tid = threadIdx.x;
+  // count slot W[L-1] (k_round_counts_narrow folded it exactly as element L-1 is)
+  double den = 0.0, cnt = 0.0;
+  if (avg) {
+    cnt = cnts[q];
+    den = secure ? 1e12 * cnt : cnt;   // Math.pow(10,12) * W[last] (IPLS.java:1167)
+  }
+  auto add = [](double (&a)[E], const V& v) {
+#pragma unroll
+    for (int c = 0; c < E; ++c) a[c] = a[c] + S::template get<E>(v, c);
+  };
+  auto init = [&](double (&a)[E], int64_t o) {
+    if constexpr (START == kZero) {
+#pragma unroll
+      for (int c = 0; c < E; ++c) a[c] = 0.0;
+    } else {
+#pragma unroll
+      for (int c = 0; c < E / 2; ++c) {
+        const d2 x = decode2<false>(ld16<false>(agg + o + 2 * c));
+        a[2 * c] = x.x, a[2 * c + 1] = x.y;
+      }
+    }
+  };
+  auto quot = [&](double w) -> unsigned { return A::narrow((float)(cnt == 0.0 ? w : w / den)); };
+  // fused epilogue for element e holding fold value a, element by element
+  auto fin1 = [&](int64_t e, double a) {
+    const double w = a + (rep ? __builtin_bit_cast(double, ld8(rep + e)) : 0.0);
+    st8(dst + e, __builtin_bit_cast(unsigned long long, w));
+    if (avg && e < L - 1) st_avg1<A>(avg + e, quot(w));
+  };
+
+  if (base + kTile <= L) {
+    const int64_t o0 = base + E * (int64_t)tid;
+    double acc[R][E];
+#pragma unroll
+    for (int r = 0; r < R; ++r) init(acc[r], o0 + (int64_t)r * BS * E);
+    if constexpr (PF) {
+      V v[R];
+      if (0 < k) {
+        const T* __restrict__ src = pb[0] + o0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = ldu(src + (int64_t)r * BS * E);
+      }
+      for (int j = 0; j < k; ++j) {
+        V nx[R];
+        if (j + 1 < k) {
+          const T* __restrict__ src = pb[j + 1] + o0;
+#pragma unroll
+          for (int r = 0; r < R; ++r) nx[r] = ldu(src + (int64_t)r * BS * E);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) add(acc[r], v[r]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = nx[r];
+      }
+    } else {
+      for (int j = 0; j < k; ++j) {
+        const T* __restrict__ src = pb[j] + o0;
+        V v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = ldu(src + (int64_t)r * BS * E);
+#pragma unroll
+        for (int r = 0; r < R; ++r) add(acc[r], v[r]);
+      }
+    }
+    // W = fold + REP, and the averages' R stores before W's (as in k_round)
+    const int m = (int)(((uintptr_t)avg / sizeof(O)) & 3);
+    const int lane = tid & 63;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t o = o0 + (int64_t)r * BS * E;
+      if (rep) {
+#pragma unroll
+        for (int c = 0; c < E / 2; ++c) {
+          const d2 y = decode2<false>(ld16<true>(rep + o + 2 * c));
+          acc[r][2 * c] = acc[r][2 * c] + y.x;
+          acc[r][2 * c + 1] = acc[r][2 * c + 1] + y.y;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < E; ++c) acc[r][c] = acc[r][c] + 0.0;   // AGG + REP with REP == +0.0
+      }
+      if (avg) {
+        const unsigned y0 = quot(acc[r][0]), y1 = quot(acc[r][1]), y2 = quot(acc[r][2]), y3 = quot(acc[r][3]);
+        if (m == 0) {
+          // element o + 3 may be the count slot L-1, which is not output
+          if (o + 3 < L - 1) {
+            st_avg4<A>(avg + o, y0, y1, y2, y3);
+          } else {
+            st_avg1<A>(avg + o, y0);
+            st_avg1<A>(avg + o + 1, y1);
+            st_avg1<A>(avg + o + 2, y2);
+          }
+        } else {
+          // avg + o is m elements past a 16-B (floats) / 8-B (16-bit) boundary: lane t writes the aligned
+          // group (o + 4 - m .. o + 7 - m) = its own last m values and lane t+1's first 4 - m
+          const unsigned n0 = __shfl_down(y0, 1), n1 = __shfl_down(y1, 1), n2 = __shfl_down(y2, 1);
+          unsigned g0, g1, g2, g3;
+          if (m == 1) g0 = y3, g1 = n0, g2 = n1, g3 = n2;
+          else if (m == 2) g0 = y2, g1 = y3, g2 = n0, g3 = n1;
+          else g0 = y1, g1 = y2, g2 = y3, g3 = n0;
+          if (lane < 63) {
+            st_avg4<A>(avg + o + 4 - m, g0, g1, g2, g3);
+          } else {
+            // the wave's last m values (the very last may be the count slot L-1)
+            if (m >= 3) st_avg1<A>(avg + o + 1, y1);
+            if (m >= 2) st_avg1<A>(avg + o + 2, y2);
+            if (o + 3 < L - 1) st_avg1<A>(avg + o + 3, y3);
+          }
+          if (lane == 0) {   // the wave's first 4 - m values
+            st_avg1<A>(avg + o, y0);
+            if (m <= 2) st_avg1<A>(avg + o + 1, y1);
+            if (m <= 1) st_avg1<A>(avg + o + 2, y2);
+          }
+        }
+      }
+    }
+    // W: the 8 lanes that own two adjacent 128-B lines swap their upper pair
+    // of sums with lane ^ 4, so each store instruction writes whole lines
+    // (k_reduce_narrow's E == 4 stores)
+    const bool hi = tid & 4;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t o = o0 + (int64_t)r * BS * 4;
+      const d2 own = d2{acc[r][0], acc[r][1]};
+      const d2 got = d2{__shfl_xor(acc[r][2], 4), __shfl_xor(acc[r][3], 4)};   // elements o ^ 16 .. + 2, + 3
+      __builtin_nontemporal_store(encode2<false>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
+      __builtin_nontemporal_store(encode2<false>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
+    }
+    return;
+  }
+  // ------- partial last tile: 4*BS-element vector steps, scalar remainder -------
+  const int64_t end = base + kTile < L ? base + kTile : L;
+  int64_t sb = base;
+  for (; sb + E * BS <= end; sb += E * BS) {
+    const int64_t o = sb + E * (int64_t)tid;
+    double a[E];
+    init(a, o);
+    int jj = 0;
+    for (; jj + kPBV <= k; jj += kPBV) {
+      V v[kPBV];
+#pragma unroll
+      for (int g = 0; g < kPBV; ++g) v[g] = ldu(pb[jj + g] + o);
+#pragma unroll
+      for (int g = 0; g < kPBV; ++g) add(a, v[g]);
+    }
+    for (; jj < k; ++jj) add(a, ldu(pb[jj] + o));
+#pragma unroll
+    for (int c = 0; c < E; ++c) fin1(o + c, a[c]);
+  }
+  for (int64_t e = sb + tid; e < end; e += BS) {
+    double acc;
+    if constexpr (START == kZero) acc = 0.0;
+    else acc = decode1<false>(ld8(agg + e));
+    int jj = 0;
+    for (; jj + kPB <= k; jj += kPB) {
+      typename S::raw v[kPB];
+#pragma unroll
+      for (int g = 0; g < kPB; ++g) v[g] = S::ldraw(pb[jj + g] + e);
+#pragma unroll
+      for (int g = 0; g < kPB; ++g) acc = acc + S::widen(v[g]);
+    }
+    for (; jj < k; ++jj) acc = acc + S::widen(S::ldraw(pb[jj] + e));
+    fin1(e, acc);
+  }
+}
+
+// Count slot of a fused narrow round, one wave per partition: k_round_counts
+// with the format's widening load --
+// cnt = ((init[L-1] | +0.0) + b_0[L-1] + ... + b_{k-1}[L-1]) + (REP[L-1] | +0.0),
+// the identical expression in the identical order, so the bits element L-1 of
+// the round gets.
+template <class S, int START>
+__global__ __launch_bounds__(64) void k_round_counts_narrow(const typename S::elem* const* __restrict__ bufs,
+                                                            const PartDesc* __restrict__ parts, int k, int n_parts,
+                                                            double* __restrict__ cnts) {
+  const int q = blockIdx.x;
+  if (q >= n_parts) return;
+  const int lane = threadIdx.x;
+  const PartDesc d = parts[q];
+  const int64_t e = d.len - 1;
+  const typename S::elem* const* pb = bufs + (size_t)q * k;
+  double c = (START == kZero) ? 0.0 : __builtin_bit_cast(double, ld8(d.init + e));
+  for (int j0 = 0; j0 < k; j0 += 64) {
+    const int j = j0 + lane;
+    const double v = j < k ? S::widen(S::ldraw(pb[j] + e)) : 0.0;
+    const int m = k - j0 < 64 ? k - j0 : 64;
+    for (int t = 0; t < m; ++t) c = c + __shfl(v, t);
+  }
+  if (lane == 0) cnts[q] = c + (d.rep ? __builtin_bit_cast(double, ld8(d.rep + e)) : 0.0);
+}
+
 }  // namespace ipls

@@ -30,6 +30,7 @@ SAVED_SET, SAVED_BLEND = 0, 1
 KERNEL_REDUCE, KERNEL_ROUND, KERNEL_FOLD1, KERNEL_REDUCE_SCALAR = 1, 2, 3, 4
 KERNEL_REDUCE_F32 = 5
 KERNEL_REDUCE_H16 = 6
+KERNEL_ROUND_F32, KERNEL_ROUND_H16 = 7, 8
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2

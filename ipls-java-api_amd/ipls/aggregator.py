@@ -629,7 +629,15 @@ class Aggregator:
         ``out`` (or ``dtype=np.float16`` / ``dtype="bf16"``, the latter a
         uint16 array of bit patterns) gets that float rounded again to the
         16-bit format (include/ipls_agg.h: two roundings, what narrowing the
-        f32 output gives)."""
+        f32 output gives).
+        One launch means: f64 buckets with f64 averages (k_round), and f32 /
+        half / bf16 buckets with no averages or f32 / half / bf16 ones
+        (k_round_narrow; ``with_average=False``, an ``out`` of one of these
+        dtypes, or such a ``dtype=``), every bucket 16-B aligned.  Everything
+        else -- a bucket off a 16-B boundary, f32 / half / bf16 buckets with
+        the default f64 averages, f64 buckets with narrowed averages -- runs
+        the fold, AggregatePartition and the divide as three launches inside
+        the call, with the same bits."""
         n_parts = len(buckets)
         flat, k, kind = _bucket_table_kind(buckets, self.lengths, p_first, big_endian)
         arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
