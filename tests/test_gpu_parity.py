@@ -680,8 +680,10 @@ def test_degenerate_batches(ipls, O):
 
 
 def test_many_partitions_small_buckets(ipls, O):
-    """-pa much larger than the GPU: 300 partitions of an odd model size in
-    one batch launch (small shape), vs the oracle."""
+    """-pa much larger than the GPU: 300 partitions of an odd model size,
+    filled by UpdateGradient (a split per peer: no batched fold is issued),
+    aggregated one partition at a time and divided by GetPartitions, vs the
+    oracle."""
     M, P, K = 100003, 300, 3
     agg = ipls.Aggregator(M, P)
     flats = [O.synth_bucket(M, 1, k) for k in range(K)]

@@ -12,6 +12,10 @@ ipls_agg_last_launch that it reached the shape it was written for, then
 compares with the oracle: bit for bit on whole partitions (C oracle,
 oracle/ipls_oracle.c) and by per-partition checksums of the counter
 workload (tests/golden/golden.json "full", config D = 64 x 4M x 32 in full).
+Division of labour: production sizes and checksums here; the seams of the
+same shapes (lengths around a tile, K across the peer groups, special values,
+guard bands, ragged and tiny partitions, every launch record) in
+tests/test_gpu_wide_small.py, at the smallest batches that reach them.
 References: MyIPFSClass.java:444-455 (GetParameters BE decode),
 :105-116 (update_file BE encode), Decentralized_Storage_Receiver.java:239-257
 (FIRST-start merge), Updater.java:115-117 (the fold), IPLS.java:1248-1274 and
