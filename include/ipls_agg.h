@@ -119,8 +119,14 @@ extern "C" {
  *            ipls_agg_reduce_batch, ipls_agg_reduce_batch_out, ipls_agg_aggregate_round
  *            (bufs: DEV_F32; the destinations stay F64 / BE)
  *   outputs: ipls_agg_get_partitions (out_kind), ipls_agg_aggregate_round (avg_kind)
+ *   streamed: ipls_agg_accumulate_chunked_narrow (HOST_F32 source),
+ *            ipls_agg_get_partitions_chunked_narrow (HOST_F32 output); the JNI shim's
+ *            float[] natives (accumulateFloats, getPartitionsFloats, updateGradientFloats,
+ *            loadModelFloats) sit on these and on update_gradient / load_model
  * Every other call stays F64-only and refuses them with IPLS_E_INVAL like an unknown
- * kind: the chunked calls, accumulate_range / read_range, the JNI natives, the BE, frame
+ * kind: the F64 chunked calls (accumulate_chunked, finalize_chunked,
+ * get_partitions(_wire)_chunked -- their trainer-format twins are the two _narrow calls
+ * above), accumulate_range / read_range, the double[] / byte[] JNI natives, the BE, frame
  * and Java-serialised formats, set_weights, blend, other_replica, reduce_partial /
  * combine_partials, read, and the saved-model calls.  A count slot of an f32 bucket is
  * 1.0f.  A HOST_F32 operand crosses PCIe as 4 B per element (pinned ones too: they are
@@ -152,6 +158,8 @@ extern "C" {
  *            ipls_agg_reduce_batch, ipls_agg_reduce_batch_out, ipls_agg_aggregate_round
  *            (bufs: the DEV kinds; the destinations stay F64 / BE)
  *   outputs: ipls_agg_get_partitions (out_kind), ipls_agg_aggregate_round (avg_kind)
+ *   streamed: ipls_agg_accumulate_chunked_narrow, ipls_agg_get_partitions_chunked_narrow
+ *            (the HOST kinds)
  * Every other call refuses them with IPLS_E_INVAL, as it refuses F32.  A HOST operand
  * crosses PCIe as 2 B per element (pinned ones too: copied, not read zero-copy). */
 #define IPLS_DEV_F16     13  /* device IEEE binary16[], 2-byte aligned                        */
@@ -321,6 +329,20 @@ int ipls_agg_accumulate_range(ipls_agg *h, int p, int target, const void *src, i
  * Middleware servers' is a socket recv. */
 int ipls_agg_accumulate_chunked(ipls_agg *h, int p, int target, int64_t n, int src_kind, int64_t chunk,
                                 ipls_chunk_source source, void *ctx);
+
+/* ipls_agg_accumulate_chunked for a trainer's bucket: src_kind is HOST_F32,
+ * HOST_F16 or HOST_BF16 (any other kind is IPLS_E_INVAL); n, chunk (even,
+ * >= 2) and the source's offset / n count ELEMENTS, and the source writes
+ * n * s bytes (s = 4 or 2) of the format into dst.  The values cross PCIe as
+ * s bytes each and are widened in the fold (k_fold1_narrow from the call's
+ * staging), so the bits are those of ipls_agg_accumulate(HOST_F32 / F16 /
+ * BF16) on the whole bucket, i.e. of the F64 call fed the widened values.
+ * Every rule of ipls_agg_accumulate_chunked holds word for word: no lock
+ * while the source runs, the arrival takes effect as one unit when its last
+ * chunk has landed, all or nothing, n < L_p is IPLS_E_RANGE before any source
+ * call.  The JNI shim's accumulateFloats(float[]) sits on it. */
+int ipls_agg_accumulate_chunked_narrow(ipls_agg *h, int p, int target, int64_t n, int src_kind, int64_t chunk,
+                                       ipls_chunk_source source, void *ctx);
 
 /* The reverse of a ranged fold, asynchronous: target[offset .. offset+n) of
  * partition p is copied into pinned host memory dst (ipls_host_alloc), as
@@ -563,6 +585,20 @@ int ipls_agg_get_partitions(ipls_agg *h, void *out, int64_t n, int out_kind);
  * ipls_agg_get_partitions. */
 int ipls_agg_get_partitions_chunked(ipls_agg *h, int64_t chunk, ipls_chunk_sink sink, void *ctx);
 
+/* ipls_agg_get_partitions_chunked with the model narrowed to a trainer
+ * format on the GPU: out_kind is HOST_F32, HOST_F16 or HOST_BF16 (any other
+ * kind is IPLS_E_INVAL), and the values are exactly those of
+ * ipls_agg_get_partitions with that kind (one rounding of the double quotient
+ * to float, then for the 16-bit kinds the second rounding).  The snapshot is
+ * model_size * s bytes (s = 4 or 2); `chunk` counts ELEMENTS (even, >= 2);
+ * the sink gets BYTES: sink(ctx, bytes, offset, n) with `offset` and `n` in
+ * bytes of the flat narrowed model, every piece a whole number of elements.
+ * Multi-shard handles snapshot every shard first and deliver in model order.
+ * Other rules as ipls_agg_get_partitions_chunked.  The JNI shim's
+ * getPartitionsFloats(float[]) sits on it. */
+int ipls_agg_get_partitions_chunked_narrow(ipls_agg *h, int out_kind, int64_t chunk,
+                                           IPLS_BYTE_SINK_FN *sink, void *ctx);
+
 /* The same delivery as Middleware task 3's reply (Serialize, Middleware.java:
  * 164-170): each chunk is n values of the writeDouble stream -- big-endian
  * bytes, NaN canonicalised, written by the divide kernel -- so a socket sink
@@ -703,6 +739,11 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
 #define IPLS_KERNEL_ROUND_F32     7  /* k_round_narrow (fused) over DEV_F32 buckets; a tile is block x 4 x
                                         vectors elements; shape 0; seqf 1; map 3 (partial tiles first) or 0 */
 #define IPLS_KERNEL_ROUND_H16     8  /* k_round_narrow (fused) over DEV_F16 / DEV_BF16 buckets; as above */
+#define IPLS_KERNEL_FOLD1_F32     9  /* k_fold1_narrow: one F32 arrival (accumulate, accumulate_chunked_narrow),
+                                        pointers as kernel arguments; block lanes, `vectors` groups of 4
+                                        elements per lane in flight, a block's trip is 4 x block x vectors
+                                        elements, grid-stride over `grid` blocks; shape 0; seqf 1 */
+#define IPLS_KERNEL_FOLD1_H16    10  /* k_fold1_narrow: one F16 / BF16 arrival; as above */
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2
 #define IPLS_SHAPE_SMALL  3

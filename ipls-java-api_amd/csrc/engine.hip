@@ -954,12 +954,22 @@ struct FinOut {
   Fmt fmt = kFmtF64;         // their format: doubles, or with trainer-format buckets a trainer format
 };
 
+// k_fold1_narrow's launch: 4 groups of 4 elements per lane in flight (k_fold1's
+// R), and a grid of at most 2048 workgroups of 256 lanes, what 256 CUs hold at
+// once at this kernel's register count; longer buckets take further trips.
+constexpr int kFold1NarrowR = 4;
+constexpr unsigned kFold1NarrowGrid = 2048;
+
 // host_src: the bucket is pinned host memory read over PCIe (zero copy); the
 // single-bucket fold then runs on 128 workgroups, which measured 1-2.5 GB/s
 // above 256..4096 (tools/h2d_bench.hip, profiles/r01/h2d_bench_fold1.txt).
 int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, int k, Fmt fmt_in,
                int start_mode, int target, void* const* ext_dst = nullptr, bool be_out = false,
-               const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr) {
+               const FinOut* fin = nullptr, bool host_src = false, const int64_t* lens = nullptr,
+               bool arrival = false) {
+  // arrival: one trainer-format bucket of a per-arrival caller (accumulate, the
+  // chunked fold) takes k_fold1_narrow; reduce_batch never sets it and keeps
+  // k_reduce_narrow at one partition and one bucket.
   // fmt_in: what the buckets hold.  The trainer formats (floats, halves,
   // bfloat16s) are aligned to their element size; with fin they take
   // k_round_narrow, the averages (if any) in a trainer format too.
@@ -1016,6 +1026,30 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
 #undef F1
       HIP_TRY(h, hipGetLastError());
       h->last_launch = launch_info(IPLS_KERNEL_FOLD1, 0, kBlock, 4, 0, 0, blocks, be_in, be_out, kstart(start));
+      if (!ext_dst)
+        if (uint8_t* f = zero_flag(h, p_first, target)) *f = 0;
+      return IPLS_OK;
+    }
+  }
+  // the same for one arrival of a trainer format (k_fold1_narrow): the source
+  // aligned to the lane's load (16 B of floats, 8 B of 16-bit elements), the
+  // target to 16 B; any other alignment keeps the table route below
+  if (!fin && tr_in && arrival && !be_out && start != IPLS_START_FIRST && n_parts == 1 && k == 1 && bufs[0]) {
+    unsigned long long* d0 = dst_of(0);
+    const int64_t L = len_of(0);
+    if (d0 && !((uintptr_t)bufs[0] & (uintptr_t)(4 * fmt_size(fmt_in) - 1)) && !((uintptr_t)d0 & 15) && L > 0) {
+      const unsigned blocks = std::max(1u, std::min<unsigned>(blocks_for(L >> 2, kBlock * kFold1NarrowR), kFold1NarrowGrid));
+      with_narrow(fmt_in, [&](auto s) {
+        typedef decltype(s) S;
+        const auto* s0 = (const typename S::elem*)bufs[0];
+        if (start == IPLS_START_ZERO)
+          hipLaunchKernelGGL((k_fold1_narrow<S, kZero, kFold1NarrowR>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, L);
+        else
+          hipLaunchKernelGGL((k_fold1_narrow<S, kAccum, kFold1NarrowR>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, L);
+      });
+      HIP_TRY(h, hipGetLastError());
+      h->last_launch = launch_info(fmt_size(fmt_in) == 4 ? IPLS_KERNEL_FOLD1_F32 : IPLS_KERNEL_FOLD1_H16, 0, kBlock,
+                                   kFold1NarrowR, 1, 0, blocks, false, false, kstart(start));
       if (!ext_dst)
         if (uint8_t* f = zero_flag(h, p_first, target)) *f = 0;
       return IPLS_OK;
@@ -1542,7 +1576,9 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
       return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
   }
   const void* bl[1] = {dptr};
-  if (int rc = reduce_dev(h, p, 1, bl, 1, fmt_trainer(tr) ? tr : be_fmt(be), IPLS_START_ACCUM, target)) return rc;
+  if (int rc = reduce_dev(h, p, 1, bl, 1, fmt_trainer(tr) ? tr : be_fmt(be), IPLS_START_ACCUM, target, nullptr, false,
+                          nullptr, false, nullptr, /*arrival=*/true))
+    return rc;
   return staged ? release_stage(h) : IPLS_OK;
 }
 
@@ -1655,8 +1691,12 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
 // chunk has landed -- the reference's order: Middleware's Deserialize reads
 // the whole stream before UpdateModel takes PeerData.mtx (Middleware.java:224,
 // 246).  A source that stops leaves the target untouched.
-int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_kind, int64_t chunk,
-                           ipls_chunk_source source, void* ctx) {
+// The element format is a parameter: kFmtF64 / kFmtBE (the source
+// writes 8 B per value) or a trainer format (4 or 2 B per value, the fold is
+// k_fold1_narrow from the stage, 20 or 18 B per element); n, chunk and the
+// source's offsets count elements in every format.
+static int accumulate_chunked_fmt(ipls_dev* h, int p, int target, int64_t n, int src_kind, bool narrow, int64_t chunk,
+                                  ipls_chunk_source source, void* ctx) {
   if (!h || !source) return fail_nl(h, IPLS_E_INVAL, "null argument");
   if (chunk < 2 || (chunk & 1))
     return fail_nl(h, IPLS_E_INVAL, "chunk of %lld values: even and >= 2", (long long)chunk);
@@ -1664,17 +1704,20 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
   // offset is not read here: promote_future swaps AGG/FUT storage under it)
   if (p < 0 || p >= h->P) return fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", p, h->P);
   if (target < IPLS_TGT_AGG || target > IPLS_TGT_FUTURE) return fail_nl(h, IPLS_E_INVAL, "bad target %d", target);
-  if (src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE)
-    return fail_nl(h, IPLS_E_INVAL, "a chunked fold takes HOST_F64 or HOST_BE values, not kind %d", src_kind);
+  if (narrow ? !kind_trainer_host(src_kind) : (src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE))
+    return fail_nl(h, IPLS_E_INVAL, "a %schunked fold takes %s values, not kind %d", narrow ? "narrow " : "",
+                   narrow ? "HOST_F32, HOST_F16 or HOST_BF16" : "HOST_F64 or HOST_BE", src_kind);
+  const Fmt fmt = kind_fmt(src_kind);
   const int64_t L = h->len[p];
   if (n < L)   // before any source call (Updater.java:115)
-    return fail_nl(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n,
-                   (long long)L);
+    return fail_nl(h, IPLS_E_RANGE, "bucket of %lld %s shorter than partition length %lld", (long long)n,
+                   fmt_trainer(fmt) ? "values" : "doubles", (long long)L);
   HIP_TRY_NL(h, dev_use(h->device));
   const int64_t c = std::min(chunk, L);
+  const size_t esz = (size_t)fmt_size(fmt);
   ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)L * 8, (size_t)c * 8, &st)) return rc;
-  unsigned long long* d_in = (unsigned long long*)st->d;
+  if (int rc = stage_acquire(h, (size_t)L * esz, (size_t)c * esz, &st)) return rc;
+  char* d_in = (char*)st->d;
   int rc = IPLS_OK;
   auto try_hip = [&](hipError_t e, const char* what) {
     if (e != hipSuccess && !rc) {
@@ -1694,7 +1737,7 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
       break;
     }
     hipStream_t cs = st->copy[k % st->n_copy];
-    try_hip(hipMemcpyAsync(d_in + off, sl.host, (size_t)len * 8, hipMemcpyHostToDevice, cs), "hipMemcpyAsync");
+    try_hip(hipMemcpyAsync(d_in + (size_t)off * esz, sl.host, (size_t)len * esz, hipMemcpyHostToDevice, cs), "hipMemcpyAsync");
     try_hip(hipEventRecord(sl.ev, cs), "hipEventRecord");
     if (!rc) sl.pending = true;
   }
@@ -1718,7 +1761,9 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
       }
     }
     const void* bl[1] = {d_in};
-    if (!rc) rc = reduce_dev(h, p, 1, bl, 1, be_fmt(src_kind == IPLS_HOST_BE), IPLS_START_ACCUM, target);
+    if (!rc)
+      rc = reduce_dev(h, p, 1, bl, 1, fmt, IPLS_START_ACCUM, target, nullptr, false, nullptr, false, nullptr,
+                      /*arrival=*/true);
     // whatever ran, nothing queued on the shard stream after this point reads `d`
     if (hipEventRecord(st->free_ev, h->stream) == hipSuccess) {
       st->free_pending = true;
@@ -1734,6 +1779,18 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
   }
   stage_release(h, st);
   return rc;
+}
+
+int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_kind, int64_t chunk,
+                           ipls_chunk_source source, void* ctx) {
+  return accumulate_chunked_fmt(h, p, target, n, src_kind, false, chunk, source, ctx);
+}
+
+// The same call for a trainer's float, half or bfloat16 bucket: 4 or 2 B per
+// value through the source, the ring and PCIe, widened in the fold.
+int dev_accumulate_chunked_narrow(ipls_dev* h, int p, int target, int64_t n, int src_kind, int64_t chunk,
+                                  ipls_chunk_source source, void* ctx) {
+  return accumulate_chunked_fmt(h, p, target, n, src_kind, true, chunk, source, ctx);
 }
 
 // A stage's device snapshot (complete once st->ready fires) handed out in
@@ -2680,21 +2737,28 @@ int dev_get_partitions(ipls_dev* h, void* out, int64_t n, int out_kind) {
 //    segment starts at flat_base); a non-zero return stops the transfer
 //    (IPLS_E_INVAL, nothing further is delivered).
 // *st is null when the engine's segment is empty.
-int dev_get_partitions_snapshot(ipls_dev* h, int64_t chunk, bool wire, ipls_stage** st_out) {
+// fmt: kFmtF64 (doubles, or with `wire` the big-endian stream), or a trainer
+// format -- the snapshot is then k_divide_narrow's, M elements of 4 or 2 B.
+int dev_get_partitions_snapshot(ipls_dev* h, int64_t chunk, bool wire, ipls_stage** st_out, Fmt fmt) {
   *st_out = nullptr;
   if (!h) return fail_nl(h, IPLS_E_INVAL, "null argument");
   if (chunk < 2 || (chunk & 1))
-    return fail_nl(h, IPLS_E_INVAL, "chunk of %lld doubles: even and >= 2", (long long)chunk);
+    return fail_nl(h, IPLS_E_INVAL, "chunk of %lld %s: even and >= 2", (long long)chunk,
+                   fmt_trainer(fmt) ? "values" : "doubles");
+  if (wire && fmt_trainer(fmt)) return fail_nl(h, IPLS_E_INVAL, "the wire stream holds doubles");
   const int64_t M = h->flat_total - h->flat_base;
   if (M <= 0) return IPLS_OK;
   HIP_TRY_NL(h, dev_use(h->device));
+  const size_t esz = (size_t)fmt_size(fmt);
   ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)M * 8, (size_t)std::min(chunk, M) * 8, &st)) return rc;
+  if (int rc = stage_acquire(h, (size_t)M * esz, (size_t)std::min(chunk, M) * esz, &st)) return rc;
   int rc = IPLS_OK;
   {
     std::lock_guard<std::mutex> lk(h->mu);
     rc = flush_pending(h);
-    if (!rc) rc = divide_range(h, 0, h->P, (unsigned long long*)st->d, wire);
+    if (!rc)
+      rc = fmt_trainer(fmt) ? divide_range_narrow(h, 0, h->P, st->d, fmt)
+                            : divide_range(h, 0, h->P, (unsigned long long*)st->d, wire);
     if (!rc) {
       const hipError_t e = hipEventRecord(st->ready, h->stream);
       if (e != hipSuccess) {
@@ -2718,6 +2782,24 @@ int dev_get_partitions_deliver(ipls_dev* h, ipls_stage* st, int64_t chunk, ipls_
   const int64_t M = h->flat_total - h->flat_base;
   HIP_TRY_NL(h, dev_use(h->device));
   return stage_deliver(h, st, M, std::min(chunk, M), h->flat_base, sink, ctx, "");
+}
+
+// Delivery of a trainer-format snapshot: bytes, at byte offsets of the flat
+// narrowed model, every piece a whole number of elements (chunk in elements).
+int dev_get_partitions_deliver_narrow(ipls_dev* h, ipls_stage* st, int64_t chunk, Fmt fmt, ipls_byte_sink sink,
+                                      void* ctx) {
+  if (!st) return IPLS_OK;
+  const int64_t M = h->flat_total - h->flat_base, esz = fmt_size(fmt);
+  HIP_TRY_NL(h, dev_use(h->device));
+  const int64_t base = h->flat_base * esz;
+  const int rc = stage_ring(h, st, (const char*)st->d, M * esz, std::min(chunk, M) * esz,
+                            [&](const void* host, int64_t off, int64_t len) {
+                              if (sink(ctx, (const uint8_t*)host, base + off, len) == 0) return IPLS_OK;
+                              return fail_nl(h, IPLS_E_INVAL, "the byte sink stopped the transfer at offset %lld",
+                                             (long long)(base + off));
+                            });
+  stage_release(h, st);
+  return rc;
 }
 
 // A snapshot that is not delivered (another shard failed first): the divide

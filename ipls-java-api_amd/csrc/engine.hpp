@@ -72,13 +72,19 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
 int dev_read_range(ipls_dev* h, int p, int target, void* dst, int64_t off, int64_t n, int dst_kind, uint64_t* ticket);
 int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_kind, int64_t chunk,
                            ipls_chunk_source source, void* ctx);
+int dev_accumulate_chunked_narrow(ipls_dev* h, int p, int target, int64_t n, int src_kind, int64_t chunk,
+                                  ipls_chunk_source source, void* ctx);
 int dev_finalize_chunked(ipls_dev* h, int p, int sum_kind, int64_t chunk, ipls_chunk_sink sink, void* ctx);
 int dev_get_partitions_chunked(ipls_dev* h, int64_t chunk, ipls_chunk_sink sink, void* ctx, bool wire);
 // the two phases of dev_get_partitions_chunked: the snapshot under the
 // engine lock (into a stage the call owns; null for an empty segment), then
 // the delivery to the sink with no lock held, which releases the stage
-int dev_get_partitions_snapshot(ipls_dev* h, int64_t chunk, bool wire, ipls_stage** st);
+// (fmt: a trainer format makes the snapshot the narrowed model, which
+// dev_get_partitions_deliver_narrow hands out as bytes)
+int dev_get_partitions_snapshot(ipls_dev* h, int64_t chunk, bool wire, ipls_stage** st, Fmt fmt = kFmtF64);
 int dev_get_partitions_deliver(ipls_dev* h, ipls_stage* st, int64_t chunk, ipls_chunk_sink sink, void* ctx);
+int dev_get_partitions_deliver_narrow(ipls_dev* h, ipls_stage* st, int64_t chunk, Fmt fmt, ipls_byte_sink sink,
+                                      void* ctx);
 void dev_stage_release(ipls_dev* h, ipls_stage* st);
 int dev_update_indirect(ipls_dev* h, int p, int target, const void* bytes, int64_t n_bytes);
 int dev_gbuf_load(ipls_dev* h, const void* bytes, int64_t n_bytes, const void** gbuf, int64_t* glen);

@@ -661,6 +661,16 @@ int ipls_agg_accumulate_chunked(ipls_agg* H, int p, int target, int64_t n, int s
   return fwd(H, s, dev_accumulate_chunked(H->sh[s], q, target, n, src_kind, chunk, source, ctx));
 }
 
+int ipls_agg_accumulate_chunked_narrow(ipls_agg* H, int p, int target, int64_t n, int src_kind, int64_t chunk,
+                                       ipls_chunk_source source, void* ctx) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (!part_ok(H, p)) return range_err(H, p);
+  int q;
+  const int s = route(H, p, &q);
+  return fwd(H, s, dev_accumulate_chunked_narrow(H->sh[s], q, target, n, src_kind, chunk, source, ctx));
+}
+
 int ipls_agg_finalize_chunked(ipls_agg* H, int p, int sum_kind, int64_t chunk, ipls_chunk_sink sink, void* ctx) {
   KeepDevice keep_device;
   if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
@@ -1075,6 +1085,31 @@ int ipls_agg_get_partitions_chunked(ipls_agg* H, int64_t chunk, ipls_chunk_sink 
 
 int ipls_agg_get_partitions_wire_chunked(ipls_agg* H, int64_t chunk, ipls_chunk_sink sink, void* ctx) {
   return get_partitions_chunked(H, chunk, sink, ctx, true);
+}
+
+// The model narrowed to a trainer format, chunk by chunk: snapshots of every
+// shard first, then the bytes in model order (get_partitions_chunked above).
+int ipls_agg_get_partitions_chunked_narrow(ipls_agg* H, int out_kind, int64_t chunk, IPLS_BYTE_SINK_FN* sink,
+                                           void* ctx) {
+  KeepDevice keep_device;
+  if (!H || !sink) return ferr(H, IPLS_E_INVAL, "null argument");
+  if (!kind_trainer_host(out_kind))
+    return ferr(H, IPLS_E_INVAL, "a narrow chunked model takes HOST_F32, HOST_F16 or HOST_BF16, not kind %d", out_kind);
+  const Fmt fmt = kind_fmt(out_kind);
+  const std::vector<int> ss = nonempty_shards(H);
+  std::vector<ipls_stage*> st(ss.size(), nullptr);
+  int rc = IPLS_OK;
+  size_t i = 0;
+  for (; i < ss.size() && !rc; ++i)
+    rc = fwd(H, ss[i], dev_get_partitions_snapshot(H->sh[ss[i]], chunk, false, &st[i], fmt));
+  for (size_t j = 0; j < ss.size(); ++j) {
+    if (!rc && j < i) {
+      rc = fwd(H, ss[j], dev_get_partitions_deliver_narrow(H->sh[ss[j]], st[j], chunk, fmt, sink, ctx));
+    } else if (st[j]) {
+      dev_stage_release(H->sh[ss[j]], st[j]);   // after a failure: nothing more is delivered
+    }
+  }
+  return rc;
 }
 
 int ipls_agg_read(ipls_agg* H, int p, int target, void* dst, int64_t n, int dst_kind) {

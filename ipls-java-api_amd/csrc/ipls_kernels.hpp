@@ -1839,6 +1839,96 @@ __global__ __launch_bounds__(BS) void k_reduce_narrow(const typename S::elem* co
   }
 }
 
+// ---------------------------------------------------------------------------
+// k_fold1_narrow: the single-bucket fold of one arrival (k_fold1) over a
+// bucket of a narrow format, pointers passed as kernel arguments -- no table.
+//   dst[i] = start + S::widen(src[i]),  start: ZERO +0.0 | ACCUM dst[i]
+// The targets are native doubles in the arena: no BE_OUT, no FIRST.
+// A lane owns 4 consecutive elements per group: one non-temporal load through
+// ldv<4> (16 B of floats, 8 B of 16-bit elements), for ACCUM two 16-B target
+// loads, four widenings, four f64 adds.  A block's trip is kBlock * R groups
+// (4 * kBlock * R elements), a lane's R groups kBlock groups apart, all loads
+// before the adds; the blocks walk the bucket in a grid-stride loop.  A trip
+// that lies wholly inside the bucket stores through k_reduce_narrow's lane ^ 4
+// exchange, so each store instruction writes whole 128-B lines and nothing
+// outside the trip; a block's one partial trip stores every lane's own two
+// pairs.  The last L mod 4 elements go element by element from one lane.
+// src is aligned to the lane's load and dst to 16 B (decided by the host).
+// ---------------------------------------------------------------------------
+template <class S, int START, int R = 4>
+__global__ __launch_bounds__(kBlock) void k_fold1_narrow(unsigned long long* __restrict__ dst,
+                                                         const typename S::elem* __restrict__ src, int64_t L) {
+  static_assert(START == kZero || START == kAccum, "an arrival adds to +0.0 or to the target");
+  typedef typename S::elem T;
+  auto ldu = [](const T* p) { return S::unpack(S::template ldv<4>(p)); };
+  typedef decltype(ldu((const T*)nullptr)) V;
+  const int64_t n4 = L >> 2;   // whole groups
+  const int64_t trip = (int64_t)kBlock * R, stride = (int64_t)gridDim.x * trip;
+  const int tid = threadIdx.x;
+  auto sums = [](double (&a)[4], const V& v, const u2& t0, const u2& t1) {
+    if constexpr (START == kZero) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) a[c] = 0.0;
+    } else {
+      const d2 x = __builtin_bit_cast(d2, t0), y = __builtin_bit_cast(d2, t1);
+      a[0] = x.x, a[1] = x.y, a[2] = y.x, a[3] = y.y;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) a[c] = a[c] + S::template get<4>(v, c);
+  };
+  int64_t B = (int64_t)blockIdx.x * trip;
+  for (; B + trip <= n4; B += stride) {   // the whole trip in range: loads first, whole-line stores
+    const int64_t g0 = B + tid;
+    V v[R];
+    u2 t[R][2];
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = ldu(src + 4 * (g0 + (int64_t)r * kBlock));
+    if constexpr (START == kAccum) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        t[r][0] = ld16<false>(dst + 4 * (g0 + (int64_t)r * kBlock));
+        t[r][1] = ld16<false>(dst + 4 * (g0 + (int64_t)r * kBlock) + 2);
+      }
+    }
+    const bool hi = tid & 4;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      double a[4];
+      sums(a, v[r], t[r][0], t[r][1]);
+      // lanes 8m..8m+3 own one 128-B line of sums, 8m+4..8m+7 the next: the
+      // upper pairs change hands with lane ^ 4 (k_reduce_narrow's E == 4 stores)
+      const int64_t o = 4 * (g0 + (int64_t)r * kBlock);
+      const d2 own = d2{a[0], a[1]};
+      const d2 got = d2{__shfl_xor(a[2], 4), __shfl_xor(a[3], 4)};   // elements (o ^ 16) + 2, + 3
+      __builtin_nontemporal_store(encode2<false>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
+      __builtin_nontemporal_store(encode2<false>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
+    }
+  }
+  if (B < n4) {   // this block's partial trip: every lane stores its own pairs
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int64_t g = B + tid + (int64_t)r * kBlock;
+      if (g < n4) {
+        const int64_t o = 4 * g;
+        const V v = ldu(src + o);
+        u2 t0 = u2{0, 0}, t1 = u2{0, 0};
+        if constexpr (START == kAccum) t0 = ld16<false>(dst + o), t1 = ld16<false>(dst + o + 2);
+        double a[4];
+        sums(a, v, t0, t1);
+        __builtin_nontemporal_store(encode2<false>(d2{a[0], a[1]}), (gu2)(dst + o));
+        __builtin_nontemporal_store(encode2<false>(d2{a[2], a[3]}), (gu2)(dst + o + 2));
+      }
+    }
+  }
+  if ((L & 3) && blockIdx.x == 0 && tid == 0) {   // the last L mod 4 elements
+    for (int64_t e = 4 * n4; e < L; ++e) {
+      const double x = S::widen(S::ldraw(src + e));
+      const double a = ((START == kZero) ? 0.0 : __builtin_bit_cast(double, ld8(dst + e))) + x;
+      st8(dst + e, __builtin_bit_cast(unsigned long long, a));
+    }
+  }
+}
+
 // k_split over a flat vector of a narrow format: OrganizeGradients (MODE 0)
 // and UpdateGradient's own accumulate (MODE 1, 2), the expressions of k_split
 // on v = (double)flat[lo + i].  VEC (decided by the host per partition: flat +

@@ -104,6 +104,23 @@ def _out_dtype(dtype):
     return "f32" if d == np.float32 else "half" if d == np.float16 else "f64"
 
 
+def _chunked_dtype(dtype):
+    """'f32', 'half' or 'bf16' for the ``dtype=`` of UpdateChunked /
+    GetPartitionsChunked: np.float32, np.float16 or the string "bf16";
+    anything else is a ValueError (before any library call)."""
+    if isinstance(dtype, str) and dtype == "bf16":
+        return "bf16"
+    try:
+        d = np.dtype(dtype)
+    except TypeError:
+        d = None
+    if d == np.float32:
+        return "f32"
+    if d == np.float16:
+        return "half"
+    raise ValueError(f"dtype must be np.float32, np.float16 or 'bf16' (or None for doubles), not {dtype!r}")
+
+
 _NP_OUT = {"f64": np.float64, "f32": np.float32, "half": np.float16, "bf16": np.uint16}
 
 
@@ -419,7 +436,7 @@ class Aggregator:
         return t.value
 
     def UpdateChunked(self, partition: int, n: int, source, *, big_endian: bool = True, from_clients: bool = True,
-                      chunk: int = 1 << 19):
+                      chunk: int = 1 << 19, dtype=None):
         """Updater._Update of one bucket that the caller produces chunk by
         chunk, as ONE library call (ipls_agg_accumulate_chunked): ``source(dst,
         offset, count)`` writes the bucket's values [offset, offset + count)
@@ -427,26 +444,51 @@ class Aggregator:
         address ``dst`` (the library's pinned ring) and returns True; False
         stops the call with nothing folded.  ``n`` is the bucket's length
         (shorter than the partition: ArrayIndexOutOfBounds, before any
-        source call)."""
+        source call).  ``dtype=np.float32``, ``np.float16`` or ``"bf16"``: a
+        trainer's bucket (ipls_agg_accumulate_chunked_narrow) -- the source
+        writes 4*count or 2*count bytes of that format in native byte order
+        (``big_endian`` does not apply), ``n``, ``chunk``, offset and count
+        still in elements; the values are widened on the GPU."""
+        kind = None if dtype is None else _HOST_KIND[_chunked_dtype(dtype)]
         target = N.TGT_AGG if from_clients else N.TGT_REP
         caught = []
 
         @N.CHUNK_SOURCE
         def cb(ctx, dst, off, cnt):
             return _callback(caught, source, dst, off, cnt)
-        rc = self._lib.ipls_agg_accumulate_chunked(self._h, partition, target, n,
-                                                   N.HOST_BE if big_endian else N.HOST_F64, chunk, cb, None)
+        if kind is not None:
+            rc = self._lib.ipls_agg_accumulate_chunked_narrow(self._h, partition, target, n, kind, chunk, cb, None)
+        else:
+            rc = self._lib.ipls_agg_accumulate_chunked(self._h, partition, target, n,
+                                                       N.HOST_BE if big_endian else N.HOST_F64, chunk, cb, None)
         _reraise(caught)
         self._chk(rc)
 
-    def GetPartitionsChunked(self, sink, *, wire: bool = False, chunk: int = 1 << 19):
+    def GetPartitionsChunked(self, sink, *, wire: bool = False, chunk: int = 1 << 19, dtype=None):
         """GetPartitions (IPLS.java:1159-1174) handed to ``sink(ptr, offset,
         count)`` chunk by chunk in model order (ipls_agg_get_partitions_chunked,
         or with ``wire=True`` the Middleware task-3 writeDouble stream,
         ipls_agg_get_partitions_wire_chunked): 8*count bytes at ``ptr`` in
         the library's pinned ring, valid during the call; the sink returns
-        True to go on."""
+        True to go on.  ``dtype=np.float32``, ``np.float16`` or ``"bf16"``: the
+        model narrowed on the GPU as GetPartitions(dtype=...) narrows it
+        (ipls_agg_get_partitions_chunked_narrow); the call is then ``sink(ptr,
+        byte_offset, byte_count)`` over the narrowed flat model, every piece a
+        whole number of elements, ``chunk`` still in elements.  ``wire=True``
+        holds doubles: together with a dtype it is a ValueError."""
         caught = []
+        if dtype is not None:
+            kind = _HOST_KIND[_chunked_dtype(dtype)]
+            if wire:
+                raise ValueError("wire=True is the big-endian double stream: it takes no dtype")
+
+            @N.BYTE_SINK
+            def bcb(ctx, b, off, cnt):
+                return _callback(caught, sink, ctypes.cast(b, ctypes.c_void_p).value, off, cnt)
+            rc = self._lib.ipls_agg_get_partitions_chunked_narrow(self._h, kind, chunk, bcb, None)
+            _reraise(caught)
+            self._chk(rc)
+            return
 
         @N.CHUNK_SINK
         def cb(ctx, vals, off, cnt):

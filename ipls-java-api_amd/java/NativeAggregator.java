@@ -50,9 +50,21 @@ public final class NativeAggregator implements AutoCloseable {
     /** InitializeWeights(List<Double> Model) (IPLS.java:1880-1901). */
     public void initializeWeights(double[] model) { loadModel(handle, model); }
 
+    /** InitializeWeights from the trainer's own float parameters (model.params() of a float
+     *  network): 4 B per value cross the boundary, the GPU widens each to the double
+     *  Model.java:423's toDoubleVector would have made. */
+    public void initializeWeights(float[] model) { loadModelFloats(handle, model); }
+
     /** UpdateGradient own accumulate (IPLS.java:1737-1743); gradients == null is a no-op. */
     public void updateGradient(double[] gradients, int[] authList) {
         if (gradients != null) updateGradient(handle, gradients, authList);
+    }
+
+    /** The same from the trainer's float gradient row (Model.java:423 without the
+     *  toDoubleVector widening on the heap): the bits are those of updateGradient on
+     *  the widened values.  gradients == null is a no-op. */
+    public void updateGradient(float[] gradients, int[] authList) {
+        if (gradients != null) updateGradientFloats(handle, gradients, authList);
     }
 
     /** Middleware task 2 (Deserialize, Middleware.java:156-160) + UpdateModel's
@@ -81,6 +93,14 @@ public final class NativeAggregator implements AutoCloseable {
      *  other thread waits for its heap copies.  A failed copy folds nothing. */
     public void update(double[] gradient, int p, boolean fromClients) {
         if (gradient != null) accumulate(handle, p, fromClients ? TGT_AGG : TGT_REP, gradient);
+    }
+
+    /** Updater._Update of a float bucket (count slot 1.0f): update(double[]) with 4 B per
+     *  value through the heap copy, the pinned ring and PCIe (ipls_agg_accumulate_chunked_narrow);
+     *  the GPU widens, so the bits are those of update(double[]) on the widened values.  One
+     *  library call, one ordered unit, a short array is ArrayIndexOutOfBoundsException. */
+    public void update(float[] gradient, int p, boolean fromClients) {
+        if (gradient != null) accumulateFloats(handle, p, fromClients ? TGT_AGG : TGT_REP, gradient);
     }
 
     /** Updater indirect mode (Updater.java:176-187): the `ipfs cat` bytes of a
@@ -234,6 +254,14 @@ public final class NativeAggregator implements AutoCloseable {
         return out;
     }
 
+    /** GetPartitions narrowed to float on the GPU, each quotient rounded once as Java's
+     *  (float) d rounds it (Model.java:388-390 without the double[] in between). */
+    public float[] getPartitionsFloat(int modelSize) {
+        float[] out = new float[modelSize];
+        getPartitionsFloats(handle, out);
+        return out;
+    }
+
     /** AggregatePartition for partitions [pFirst, pFirst+nParts) and their
      *  GetPartitions averages in one fused launch (ipls_agg_aggregate_round);
      *  the result is sized here from the partition geometry. */
@@ -319,6 +347,10 @@ public final class NativeAggregator implements AutoCloseable {
     private static native void updateGradient(long h, double[] flat, int[] owned);
     private static native void updateGradientDirect(long h, ByteBuffer buf, int pos, long n, int[] owned);
     private static native void accumulate(long h, int p, int target, double[] g);
+    private static native void accumulateFloats(long h, int p, int target, float[] g);
+    private static native void getPartitionsFloats(long h, float[] out);
+    private static native void updateGradientFloats(long h, float[] flat, int[] owned);
+    private static native void loadModelFloats(long h, float[] model);
     private static native void accumulateDirect(long h, int p, int target, ByteBuffer buf, int pos, long n, int kind);
     private static native long accumulateAsyncDirect(long h, int p, int target, ByteBuffer buf, int pos, long n,
                                                      int kind);

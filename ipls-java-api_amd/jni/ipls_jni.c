@@ -32,6 +32,9 @@
  * chunk keeps the thread from a safepoint, and one CPU thread's memcpy is
  * what held these natives to 33 / 21 GB/s against PCIe's 56 (VERDICT r5
  * item 4).
+ * The float[] natives (accumulateFloats, getPartitionsFloats,
+ * updateGradientFloats, loadModelFloats) move their arrays through the same
+ * critical_copy and nothing else, at every size.
  *
  * Built against the JDK's <jni.h> on the Java side's build host (make -C
  * ipls-java-api_amd jni).  This image has no JDK: tests/test_jni.py compiles
@@ -478,6 +481,119 @@ JNIEXPORT void JNICALL Java_NativeAggregator_accumulate(JNIEnv *env, jclass c, j
     const jsize n = (*env)->GetArrayLength(env, g);
     const int rc = LIB(ipls_agg_accumulate_chunked(H(h), p, tgt, n, IPLS_HOST_F64, IN_CHUNK, heap_source_fn, &hs));
     if (rc < 0 && !(*env)->ExceptionCheck(env)) throw_for(env, rc, H(h));
+}
+
+/* ---- float[] natives: the trainer's own format across the boundary ----
+ * The reference's trainer holds a float INDArray and widens it on the heap
+ * only because IPLS wants doubles (Model.java:423); these natives take the
+ * float[] as it is, 4 B per value through the heap copy, the ring and PCIe,
+ * and the GPU widens.  The arrays move only through GetArrayLength and
+ * critical_copy, at every chunk size: one short critical region per chunk,
+ * none across a library call.  jfloatArray is spelled out here as <jni.h>
+ * declares it for C (C11 allows the repeated typedef), so the shim also builds
+ * against a header that leaves the float array type out. */
+typedef jarray jfloatArray;
+static void throw_no_direct_view(JNIEnv *env) {
+    if (!(*env)->ExceptionCheck(env))
+        throw_msg(env, "java/lang/IllegalStateException", "the JVM gave no direct view of the float[]");
+}
+
+/* The chunk source of accumulateFloats: the bucket's floats [off, off + n). */
+struct heapf_source { JNIEnv *env; jarray a; };
+static int heapf_source_fn(void *ctx, void *dst, int64_t off, int64_t n) {
+    struct heapf_source *s = (struct heapf_source *)ctx;
+    /* inside the array: the library refused an array shorter than L_p before any chunk */
+    if (critical_copy(s->env, s->a, (size_t)off * 4, dst, (size_t)n * 4, 0) == 0) return 0;
+    throw_no_direct_view(s->env);
+    return 1;
+}
+
+JNIEXPORT void JNICALL Java_NativeAggregator_accumulateFloats(JNIEnv *env, jclass c, jlong h, jint p, jint tgt,
+                                                                jfloatArray g) {
+    (void)c;
+    if (!g) return;   /* Gradient == null: the Updater loops do nothing (Updater.java:115) */
+    /* accumulate(double[]) with 4-byte values: one library call for the whole
+     * arrival, the ring chunk counted in values, a short array is
+     * ArrayIndexOutOfBoundsException before any copy */
+    struct heapf_source hs = {env, g};
+    const jsize n = (*env)->GetArrayLength(env, g);
+    const int rc =
+        LIB(ipls_agg_accumulate_chunked_narrow(H(h), p, tgt, n, IPLS_HOST_F32, IN_CHUNK, heapf_source_fn, &hs));
+    if (rc < 0 && !(*env)->ExceptionCheck(env)) throw_for(env, rc, H(h));
+}
+
+/* The byte sink of getPartitionsFloats: a piece of the narrowed model from
+ * the library's pinned ring into the float[] (byte offsets of the flat model). */
+struct modelf_sink { JNIEnv *env; jarray out; };
+static int modelf_sink_fn(void *ctx, const uint8_t *bytes, int64_t off, int64_t n) {
+    struct modelf_sink *m = (struct modelf_sink *)ctx;
+    /* off + n <= 4 M <= the array's bytes (checked before the call) */
+    if (critical_copy(m->env, m->out, (size_t)off, (void *)bytes, (size_t)n, 1) == 0) return 0;
+    throw_no_direct_view(m->env);
+    return 1;
+}
+
+JNIEXPORT void JNICALL Java_NativeAggregator_getPartitionsFloats(JNIEnv *env, jclass c, jlong h, jfloatArray out) {
+    (void)c;
+    if (!out) { throw_iae(env, "null output"); return; }
+    const jsize n = (*env)->GetArrayLength(env, out);
+    int64_t M = 0;
+    int rc = LIB(ipls_agg_flat_size(H(h), &M));
+    if (rc < 0) { throw_for(env, rc, H(h)); return; }
+    if (M > n) {   /* before any copy */
+        throw_msg(env, "java/lang/ArrayIndexOutOfBoundsException", "float[] shorter than the model");
+        return;
+    }
+    if (M >= 2 * RING_CHUNK) {
+        /* pipelined: the narrowing divide once on the GPU, then ring-sized pieces */
+        struct modelf_sink ms = {env, out};
+        rc = LIB(ipls_agg_get_partitions_chunked_narrow(H(h), IPLS_HOST_F32, RING_CHUNK, modelf_sink_fn, &ms));
+        if (rc < 0 && !(*env)->ExceptionCheck(env)) throw_for(env, rc, H(h));
+        return;
+    }
+    float *dst = (float *)stage(env, 0, (size_t)M * 4);
+    if (!dst) return;
+    rc = LIB(ipls_agg_get_partitions(H(h), dst, M, IPLS_HOST_F32));
+    if (rc < 0) { throw_for(env, rc, H(h)); return; }
+    /* only the model's M values go back: elements past them keep theirs */
+    if (M > 0 && critical_copy(env, out, 0, dst, (size_t)M * 4, 1) != 0) throw_no_direct_view(env);
+}
+
+JNIEXPORT void JNICALL Java_NativeAggregator_updateGradientFloats(JNIEnv *env, jclass c, jlong h, jfloatArray flat,
+                                                                    jintArray owned) {
+    (void)c;
+    if (!flat) return;   /* Gradients == null: no-op (IPLS.java:1738) */
+    if (!owned) { throw_iae(env, "null auth list"); return; }
+    const jsize n = (*env)->GetArrayLength(env, flat), no = (*env)->GetArrayLength(env, owned);
+    float *src = (float *)stage(env, 0, (size_t)n * 4);
+    if (!src) return;
+    jint *own = (*env)->GetIntArrayElements(env, owned, NULL);
+    if (!own) return;   /* OutOfMemoryError pending */
+    /* only the owned partitions' slices leave the heap, as in updateGradient */
+    for (jsize i = 0; i < no; ++i) {
+        int64_t off = 0, L = 0;
+        if (LIB(ipls_agg_partition_offset(H(h), own[i], &off)) < 0 || LIB(ipls_agg_partition_len(H(h), own[i], &L)) < 0)
+            continue;
+        const int64_t hi = off + (L - 1) < (int64_t)n ? off + (L - 1) : (int64_t)n;
+        if (hi > off && critical_copy(env, flat, (size_t)off * 4, src + off, (size_t)(hi - off) * 4, 0) != 0) {
+            throw_no_direct_view(env);
+            (*env)->ReleaseIntArrayElements(env, owned, own, JNI_ABORT);
+            return;
+        }
+    }
+    int rc = LIB(ipls_agg_update_gradient(H(h), src, n, IPLS_HOST_F32, (const int32_t *)own, no));
+    (*env)->ReleaseIntArrayElements(env, owned, own, JNI_ABORT);
+    CHECK(rc, H(h));
+}
+
+JNIEXPORT void JNICALL Java_NativeAggregator_loadModelFloats(JNIEnv *env, jclass c, jlong h, jfloatArray a) {
+    (void)c;
+    if (!a) { throw_iae(env, "null model"); return; }
+    const jsize n = (*env)->GetArrayLength(env, a);
+    float *p = (float *)stage(env, 0, (size_t)n * 4);
+    if (!p) return;
+    if (n > 0 && critical_copy(env, a, 0, p, (size_t)n * 4, 0) != 0) { throw_no_direct_view(env); return; }
+    CHECK(LIB(ipls_agg_load_model(H(h), p, n, IPLS_HOST_F32)), H(h));
 }
 
 JNIEXPORT void JNICALL Java_NativeAggregator_accumulateDirect(JNIEnv *env, jclass c, jlong h, jint p, jint tgt,

@@ -10,7 +10,11 @@ copies.  One partition of L doubles:
   get_partitions_wire_chunked  the same for the divide's stream
 each at chunk sizes 2^19 .. 2^22 values, and the direct (pinned) forms beside
 them.  GB/s = 8 L / wall time per call, median of reps.
-Usage: chunk_probe.py [L] [reps] [--ab]   (--ab: one vs two copy streams, interleaved)"""
+Usage: chunk_probe.py [L] [reps] [--ab]   (--ab: one vs two copy streams, interleaved)
+       chunk_probe.py [L] [reps] --float   the trainer-format calls against the F64 ones, rep by rep in one
+                                           process: accumulate_chunked_narrow(HOST_F32) vs accumulate_chunked,
+                                           get_partitions_chunked_narrow(HOST_F32) vs get_partitions_chunked;
+                                           values per second (the float calls move half the bytes per value)"""
 import ctypes
 import json
 import sys
@@ -76,9 +80,48 @@ def ab():
     print(json.dumps(out))
 
 
+def float_mode():
+    """F32 vs F64 chunked calls on one handle, interleaved rep by rep; the
+    callbacks return at once, so the library's pipeline alone is timed."""
+    agg = ipls.Aggregator(n_partitions=1, bucket_len=L)
+    lib, h = agg._lib, agg._h
+    src = N.CHUNK_SOURCE(lambda ctx, dst, off, n: 0)
+    sink = N.CHUNK_SINK(lambda ctx, vals, off, n: 0)
+    bsink = N.BYTE_SINK(lambda ctx, b, off, n: 0)
+    out = {"L": L, "reps": reps, "mode": "float vs double, interleaved in one process", "unit": "Gvalues/s"}
+    for chunk in (1 << 19, 1 << 20, 1 << 21, 1 << 22):
+        ops = {
+            "accumulate_chunked": {
+                "f64": lambda: (lib.ipls_agg_accumulate_chunked(h, 0, N.TGT_AGG, L, N.HOST_F64, chunk, src, None),
+                                agg.sync()),
+                "f32": lambda: (lib.ipls_agg_accumulate_chunked_narrow(h, 0, N.TGT_AGG, L, N.HOST_F32, chunk, src,
+                                                                       None), agg.sync())},
+            "get_partitions_chunked": {
+                "f64": lambda: lib.ipls_agg_get_partitions_chunked(h, chunk, sink, None),
+                "f32": lambda: lib.ipls_agg_get_partitions_chunked_narrow(h, N.HOST_F32, chunk, bsink, None)},
+        }
+        row = {}
+        for name, pair in ops.items():
+            ts = {k: [] for k in pair}
+            for fn in pair.values():
+                fn()
+            for _ in range(reps):
+                for k, fn in pair.items():
+                    t0 = time.perf_counter()
+                    fn()
+                    ts[k].append(time.perf_counter() - t0)
+            row[name] = {k: round(L / float(np.median(v)) / 1e9, 3) for k, v in ts.items()}
+            row[name]["f32_over_f64"] = round(row[name]["f32"] / row[name]["f64"], 3)
+        out[f"chunk_{chunk}"] = row
+    agg.close()
+    print(json.dumps(out))
+
+
 def main():
     if "--ab" in sys.argv:
         return ab()
+    if "--float" in sys.argv:
+        return float_mode()
     agg = ipls.Aggregator(n_partitions=1, bucket_len=L)
     lib, h = agg._lib, agg._h
     src = N.CHUNK_SOURCE(lambda ctx, dst, off, n: 0)

@@ -16,7 +16,9 @@ One partition of L doubles (one bucket per call, as the Updater folds):
                                   a pinned direct buffer
 GB/s = bytes of the Java-side array / wall time per call (median of reps).
 Usage: jni_heap_probe.py [L] [reps] [--ab-slots=2,3,4]
-(--ab-slots: the stage ring depth, one handle per value, interleaved in one process)"""
+(--ab-slots: the stage ring depth, one handle per value, interleaved in one process)
+       jni_heap_probe.py [L] [reps] --float   accumulateFloats / getPartitionsFloats against accumulate(double[]) /
+                                              getPartitions(double[]), rep by rep in one process; values per second"""
 import ctypes
 import json
 import os
@@ -93,6 +95,38 @@ if _ab:
         out[name] = {f"slots_{v}": round(8 * L / float(np.median(t)) / 1e9, 2) for v, t in ts.items()}
     for hv in hs.values():
         jvm.call("close", hv)
+    jvm.call("close", h)
+    print(json.dumps(out))
+    sys.exit(0)
+
+if "--float" in sys.argv:
+    from ipls import _native as N
+    lib, hv = N.lib(), ctypes.c_void_p(h.value)
+    farr = jvm.ints(g.astype(np.float32).view(np.int32))      # a float[]: 4-byte elements
+    model = jvm.doubles(np.zeros(L - 1))
+    fmodel = jvm.ints(np.zeros(L - 1, dtype=np.int32))
+
+    def synced(name, *args):
+        assert jvm.call(name, *args)[1] is None
+        assert lib.ipls_agg_sync(hv) == 0       # accumulate returns once its fold is queued
+    ops = {"accumulate": {"double[]": lambda: synced("accumulate", h, 0, 0, arr),
+                          "float[]": lambda: synced("accumulateFloats", h, 0, 0, farr)},
+           "getPartitions": {"double[]": lambda: synced("getPartitions", h, model),
+                             "float[]": lambda: synced("getPartitionsFloats", h, fmodel)}}
+    out = {"L": L, "reps": reps, "mode": "float[] vs double[], interleaved in one process", "unit": "Gvalues/s",
+           "ring_chunk": os.environ.get("IPLS_JNI_RING_CHUNK", "default: 2097152 in, 524288 out")}
+    for name, pair in ops.items():
+        ts = {k: [] for k in pair}
+        for fn in pair.values():
+            fn()
+        for _ in range(reps):
+            for k, fn in pair.items():
+                t0 = time.perf_counter()
+                fn()
+                ts[k].append(time.perf_counter() - t0)
+        out[name] = {k: round(L / float(np.median(v)) / 1e9, 3) for k, v in ts.items()}
+        out[name]["ms"] = {k: round(float(np.median(v)) * 1e3, 3) for k, v in ts.items()}
+        out[name]["float_over_double"] = round(out[name]["float[]"] / out[name]["double[]"], 3)
     jvm.call("close", h)
     print(json.dumps(out))
     sys.exit(0)
