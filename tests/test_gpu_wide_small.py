@@ -22,6 +22,10 @@ and one quiet NaN with a payload (never two different NaNs nor inf - inf in
 one element: a single NaN operand propagates unchanged on the CPU and through
 v_add_f64 alike, so those bits are compared raw as well).
 
+tests/test_gpu_peer_counts.py drives the same Rig at K = 8, 17, 65 with a pool
+of its own (65 buckets with witness columns, rotated by columns instead of by
+peer: Rig's pool, classes and shift parameters).
+
 Every case makes one launch, asserts the whole launch record
 (check_record), and compares bits: caller-owned outputs in full on the device
 between sentinel guard bands, handle targets by the checksum of every
@@ -168,10 +172,10 @@ def seam_positions(L):
     return sorted(e for e in pos if 0 <= e < L - 1)
 
 
-def make_pool(O, L, count=1.0, count_at=()):
-    """KMAX buckets of L doubles; element L - 1 (and len - 1 for each shorter
+def make_pool(O, L, count=1.0, count_at=(), kmax=KMAX):
+    """kmax buckets of L doubles; element L - 1 (and len - 1 for each shorter
     partition length in count_at) is the count slot."""
-    h = np.stack([O.synth_bucket(L, 7, j) * 10.0 ** (j % 7 - 3) for j in range(KMAX)])
+    h = np.stack([O.synth_bucket(L, 7, j) * 10.0 ** (j % 7 - 3) for j in range(kmax)])
     for n, e in enumerate(seam_positions(L)):
         kind = n % 8
         if kind in (0, 7):      # cancels in one order only: 1e16 + x - 1e16 != 1e16 - 1e16 + x
@@ -179,7 +183,7 @@ def make_pool(O, L, count=1.0, count_at=()):
         elif kind == 1:         # -0.0 everywhere: FIRST keeps it, ZERO (+0.0 + -0.0) and + REP do not
             h[:, e] = -0.0
         elif kind == 2:         # subnormals only: flushing them to zero would show
-            h[:, e] = 5e-324 * (np.arange(KMAX) + 1)
+            h[:, e] = 5e-324 * (np.arange(kmax) + 1)
         elif kind == 3:
             h[2, e], h[5, e] = 1e300, -1e300
         elif kind == 5:
@@ -215,9 +219,19 @@ def same_device(got, want, what):
 
 
 class Rig:
-    """One handle, one pool, and the three launches under test."""
+    """One handle, one pool, and the three launches under test.
 
-    def __init__(self, ipls, O, P=0, L=0, *, model=None, secure=False, count=1.0, count_at=()):
+    The pool is make_pool's `kmax` buckets, rotated by peer: partition p folds
+    buckets p, p + 1, .. (mod kmax), so there are kmax rotation classes.  Or
+    the caller gives `pool` (tests/test_gpu_peer_counts.py): its rows are the
+    peers' buckets in order, then the bucket an ACCUM case starts from and the
+    REP bucket, each `shift` * (classes - 1) columns wider than a partition;
+    partition p then folds the same peers in the same order from column
+    (p mod classes) * shift on -- a rotation by columns, under which peer 0
+    stays peer 0."""
+
+    def __init__(self, ipls, O, P=0, L=0, *, model=None, secure=False, count=1.0, count_at=(), kmax=KMAX,
+                 pool=None, classes=0, shift=0):
         self.ipls, self.O, self.secure = ipls, O, secure
         if model:
             self.agg = ipls.Aggregator(model[0], model[1], secure=secure)
@@ -225,10 +239,15 @@ class Rig:
             self.agg = ipls.Aggregator(n_partitions=P, bucket_len=L, secure=secure)
         self.P, self.lens, self.offs = self.agg.n_partitions, self.agg.lengths, self.agg.offsets
         self.L = max(self.lens)
-        self.h = make_pool(O, self.L, count, count_at)
-        self.stride = (self.L + 63) // 32 * 32            # even: every bucket 16-B aligned
-        host = np.zeros((KMAX, self.stride))
-        host[:, :self.L] = self.h
+        if pool is None:
+            self.h, self.kmax, self.C, self.shift = make_pool(O, self.L, count, count_at, kmax), kmax, kmax, 0
+        else:
+            assert shift > 0 and shift % 2 == 0 and pool.shape[1] == self.L + (classes - 1) * shift
+            self.h, self.kmax, self.C, self.shift = pool, pool.shape[0] - 2, classes, shift
+        width = self.h.shape[1]
+        self.stride = (width + 63) // 32 * 32             # even: every bucket 16-B aligned
+        host = np.zeros((self.h.shape[0], self.stride))
+        host[:, :width] = self.h
         self.native, self.be = dev_bits(host), dev_bits(host, be=True)
         torch.cuda.synchronize()   # uploads ran on torch's stream; the handle's does not order after it
 
@@ -240,18 +259,29 @@ class Rig:
         self.native = self.be = None
         torch.cuda.empty_cache()
 
+    def _src(self, c, i, first):
+        """(pool row, first column) of bucket i of a partition of rotation class c."""
+        if self.shift:
+            return {0: i, PRIOR: self.kmax, REPB: self.kmax + 1}[first], c * self.shift
+        return (c + first + i) % self.kmax, 0
+
     def rows(self, parts, K, be, first=0):
-        """Bucket table: partition p folds pool buckets p + first, p + first + 1, .. (mod KMAX)."""
+        """Bucket table: partition p folds pool buckets p + first, p + first + 1, .. (mod kmax), or with a
+        caller's pool buckets 0, 1, .. from its class's column on (first: the PRIOR or the REP bucket alone)."""
         base = int((self.be if be else self.native).data_ptr())
-        return [[self.ipls.DeviceBuffer(base + 8 * ((p + first + i) % KMAX) * self.stride, self.lens[p], big_endian=be)
-                 for i in range(K)] for p in parts]
+        out = []
+        for p in parts:
+            src = [self._src(p % self.C, i, first) for i in range(K)]
+            out.append([self.ipls.DeviceBuffer(base + 8 * (r * self.stride + col), self.lens[p], big_endian=be)
+                        for r, col in src])
+        return out
 
     def bufs(self, c, n, K, first=0):
-        return [self.h[(c + first + i) % KMAX][:n] for i in range(K)]
+        return [self.h[r][col:col + n] for r, col in (self._src(c, i, first) for i in range(K))]
 
     def full_reads(self, parts, extra=()):
         parts = list(parts)
-        return sorted(set(parts[:2 * KMAX] + parts[-2:] + list(extra)))
+        return sorted(set(parts[:2 * self.C] + parts[-2:] + list(extra)))
 
     # ---- k_reduce into caller buffers (reduce_batch_out), guard bands around every partition ----
     def reduce_out(self, K, be_in, be_out, start, shape, mapping, p_first=0, n=None):
@@ -263,13 +293,14 @@ class Rig:
         stride = GUARD + (L + 1) // 2 * 2 + GUARD
         out = torch.full((n, stride), SENTINEL, dtype=torch.int64, device="cuda")
         want = out.clone()
-        cls = torch.arange(p_first, p_first + n, device="cuda") % KMAX
-        prior = [None] * KMAX
+        C = self.C                                        # rotation classes
+        cls = torch.arange(p_first, p_first + n, device="cuda") % C
+        prior = [None] * C
         if start == ipls.START_ACCUM:   # the destination holds a bucket, in the byte order it is written in
-            prior = [self.h[(c + PRIOR) % KMAX][:L] for c in range(KMAX)]
+            prior = [self.bufs(c, L, 1, PRIOR)[0] for c in range(C)]
             out[:, GUARD:GUARD + L] = dev_bits(np.stack(prior), be_out)[cls]
         with np.errstate(all="ignore"):
-            exp = np.stack([O.reduce(self.bufs(c, L, K), L, start, prior[c]) for c in range(KMAX)])
+            exp = np.stack([O.reduce(self.bufs(c, L, K), L, start, prior[c]) for c in range(C)])
         want[:, GUARD:GUARD + L] = dev_bits(exp, be_out)[cls]
         dsts = [ipls.DeviceBuffer(int(out.data_ptr()) + 8 * (q * stride + GUARD), L, big_endian=be_out)
                 for q in range(n)]
@@ -293,20 +324,20 @@ class Rig:
                      max(self.lens[p] for p in parts))
         exp = {}
         for p in parts:
-            key = (p % KMAX, self.lens[p])
+            key = (p % self.C, self.lens[p])
             if key not in exp:
                 c, Lq = key
                 with np.errstate(all="ignore"):
-                    acc = self.h[(c + PRIOR) % KMAX][:Lq] if start == ipls.START_ACCUM else None
+                    acc = self.bufs(c, Lq, 1, PRIOR)[0] if start == ipls.START_ACCUM else None
                     e = O.reduce(self.bufs(c, Lq, K), Lq, start, acc)
                 exp[key] = (e, O.checksum(e))
             assert agg.checksum(p) == exp[key][1], f"AGG[{p}] checksum, K={K} be_in={be_in} start={start}"
         for p in self.full_reads(parts):
-            same_bits(agg.read(p), exp[(p % KMAX, self.lens[p])][0], f"AGG[{p}] K={K} be_in={be_in} start={start}")
+            same_bits(agg.read(p), exp[(p % self.C, self.lens[p])][0], f"AGG[{p}] K={K} be_in={be_in} start={start}")
 
     # ---- k_round (aggregate_round): W to the handle, averages to a guarded device buffer ----
     def round(self, K, be_in, accum, shift, shape, mapping, p_first=0, n=None, with_average=True, rep=True):
-        ipls, O, agg = self.ipls, self.O, self.agg
+        ipls, O, agg, C = self.ipls, self.O, self.agg, self.C
         n = self.P - p_first if n is None else n
         parts = list(range(p_first, p_first + n))
         lens = [self.lens[p] for p in parts]
@@ -331,15 +362,15 @@ class Rig:
         exp = {}
 
         def ref(p):
-            return ref_key(p % KMAX, self.lens[p], ra <= p < rb)
+            return ref_key(p % C, self.lens[p], ra <= p < rb)
 
         def ref_key(c, Lq, has_rep):
             key = (c, Lq, has_rep)
             if key not in exp:
                 with np.errstate(all="ignore"):
-                    a = self.h[(c + PRIOR) % KMAX][:Lq] if accum else np.zeros(Lq)
+                    a = self.bufs(c, Lq, 1, PRIOR)[0] if accum else np.zeros(Lq)
                     a = O.reduce(self.bufs(c, Lq, K), Lq, O.START_ACCUM, acc=a)
-                    r = self.h[(c + REPB) % KMAX][:Lq] if has_rep else np.zeros(Lq)
+                    r = self.bufs(c, Lq, 1, REPB)[0] if has_rep else np.zeros(Lq)
                     w = a + r
                     exp[key] = (w, O.checksum(w), O.divide(w, self.secure))
             return exp[key]
@@ -350,9 +381,9 @@ class Rig:
             assert lens[:nu] == [L0] * nu and all(self.offs[p] - self.offs[p_first] == (p - p_first) * (L0 - 1)
                                                    for p in parts)
             if L0 > 1:   # the uniform partitions: one gather per rotation class x REP on the device
-                table = dev_bits(np.stack([ref_key(c, L0, r)[2] for r in (False, True) for c in range(KMAX)]))
+                table = dev_bits(np.stack([ref_key(c, L0, r)[2] for r in (False, True) for c in range(C)]))
                 p = torch.arange(p_first, p_first + nu, device="cuda")
-                want[pos:pos + nu * (L0 - 1)] = table[p % KMAX + KMAX * ((p >= ra) & (p < rb))].flatten()
+                want[pos:pos + nu * (L0 - 1)] = table[p % C + C * ((p >= ra) & (p < rb))].flatten()
                 pos += nu * (L0 - 1)
             for p in parts[nu:]:   # a ragged last partition
                 a = ref(p)[2]
@@ -362,7 +393,7 @@ class Rig:
         same_device(buf, want, f"{what}: averages ({GUARD} guard + {n_avg} + guard)")
         for p in parts:
             assert agg.checksum(p, ipls.TGT_WEIGHTS) == ref(p)[1], f"{what}: W[{p}] checksum"
-        full = self.full_reads(parts, extra=[q for q in range(ra, min(rb, ra + 2 * KMAX))])
+        full = self.full_reads(parts, extra=[q for q in range(ra, min(rb, ra + 2 * C))])
         for p in full:
             same_bits(agg.read(p, ipls.TGT_WEIGHTS), ref(p)[0], f"{what}: W[{p}]")
         for p in (parts[0], ra if rep else parts[0], parts[-1]):
