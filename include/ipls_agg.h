@@ -344,6 +344,59 @@ int ipls_agg_accumulate_chunked(ipls_agg *h, int p, int target, int64_t n, int s
 int ipls_agg_accumulate_chunked_narrow(ipls_agg *h, int p, int target, int64_t n, int src_kind, int64_t chunk,
                                        ipls_chunk_source source, void *ctx);
 
+/* ipls_agg_update_gradient of one whole flat gradient that the caller produces
+ * chunk by chunk, as ONE call: UpdateGradient over the owned partitions
+ * (IPLS.java:1708-1743: OrganizeGradients splits everything, then the
+ * accumulate loop runs) is one step of the reference, and this is its streamed
+ * one-call form.  The bits are exactly those of ipls_agg_update_gradient on
+ * the same vector.
+ *  - src_kind is HOST_F64, HOST_BE, HOST_F32, HOST_F16 or HOST_BF16 (anything
+ *    else is IPLS_E_INVAL): one entry point for all five.  n, chunk (even,
+ *    >= 2) and the source's offset / n count ELEMENTS; the source writes
+ *    count * s bytes (s = 8, 4 or 2) into dst, the library's pinned ring.
+ *  - Every partition is bounds-checked first: a vector that overruns one
+ *    (IPLS.java:1030) is IPLS_E_RANGE, an owned index outside [0, P) is
+ *    IPLS_E_RANGE, a bad kind, chunk or a null source IPLS_E_INVAL -- all
+ *    before any source call.  n_owned == 0 is a no-op with no source call.
+ *  - For every owned p: AGG[p][i] = AGG[p][i] + v with v = (double)flat[off_p
+ *    + i] for i < ncopy_p, 1.0 at i == ncopy_p (the count slot: generated by
+ *    the kernel, it is not in the stream) and 0.0 above (the add is still
+ *    made, so a -0.0 element becomes +0.0).  A logically-zero AGG is written
+ *    as +0.0 + v without being read.  An index repeated in `owned` folds
+ *    again, in a following launch.
+ *  - Source calls: consecutive chunks, in order, covering [0, min(n, model
+ *    size)), each at most `chunk` elements; on a multi-GPU handle a chunk never
+ *    crosses the flat start of a shard, so the one before it is shorter.  The
+ *    source is called for every chunk, also where no owned partition has
+ *    values (a socket source must consume the stream); only the byte ranges of
+ *    owned partitions cross PCIe, at most one copy per owned partition a
+ *    chunk intersects.
+ *  - Order: no lock is held while the source runs.  The whole gradient takes
+ *    effect at one instant, after its last chunk has landed: the locks of the
+ *    shards that hold an owned partition are taken in ascending shard index,
+ *    all held at once, and under them each shard folds its queued arrivals,
+ *    waits (on its stream) for its copies and gets one launch of
+ *    k_update_flat over all its owned partitions.  That makes the gradient a
+ *    unit against every other call on those shards: another call sees either
+ *    none of it or all of it, in every partition.  It does not change the other
+ *    calls: ipls_agg_get_partitions_chunked still snapshots shard after shard.
+ *  - All or nothing: a non-zero source return gives IPLS_E_INVAL and leaves
+ *    EVERY accumulator, zero flag and queue as it was, on every shard; the
+ *    copies already queued are drained before the staging is reused.  The
+ *    same holds for every refusal and for any failure before the first
+ *    launch (a copy, an event, a staging allocation).  It does NOT hold for a
+ *    device failure (IPLS_E_DEVICE: the job table's upload or a launch) on a
+ *    later shard, or on the second launch of a repeated index, once an
+ *    earlier launch has been issued: what that launch folded stays folded and
+ *    its zero flags stay cleared, as after a device failure in any other call.
+ *  - Memory: each involved shard stages its flat segment (up to the last owned
+ *    value) times s bytes plus 32 bytes of padding in a device buffer of the
+ *    call's own, pooled like the staging of the other chunked calls: the pool
+ *    grows with the number of concurrent chunked calls and is freed only at
+ *    close (it is not bounded). */
+int ipls_agg_update_gradient_chunked(ipls_agg *h, int64_t n, int src_kind, const int32_t *owned, int n_owned,
+                                     int64_t chunk, ipls_chunk_source source, void *ctx);
+
 /* The reverse of a ranged fold, asynchronous: target[offset .. offset+n) of
  * partition p is copied into pinned host memory dst (ipls_host_alloc), as
  * doubles (HOST_F64) or as big-endian bytes (HOST_BE: putDouble order, what
@@ -744,6 +797,11 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
                                         elements per lane in flight, a block's trip is 4 x block x vectors
                                         elements, grid-stride over `grid` blocks; shape 0; seqf 1 */
 #define IPLS_KERNEL_FOLD1_H16    10  /* k_fold1_narrow: one F16 / BF16 arrival; as above */
+#define IPLS_KERNEL_UPDATE_FLAT  11  /* k_update_flat (update_gradient_chunked): one launch over a shard's owned
+                                        partitions; a tile is block x 2 x vectors doubles or block x 4 x vectors
+                                        trainer-format elements; grid = blocks x jobs; shape 0; seqf 1 when
+                                        every job had a full tile of values (the vector body), else 0; start
+                                        ZERO when every job's accumulator was logically zero, else ACCUM */
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2
 #define IPLS_SHAPE_SMALL  3

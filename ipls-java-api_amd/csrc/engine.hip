@@ -1793,6 +1793,181 @@ int dev_accumulate_chunked_narrow(ipls_dev* h, int p, int target, int64_t n, int
   return accumulate_chunked_fmt(h, p, target, n, src_kind, true, chunk, source, ctx);
 }
 
+// ---- the whole-gradient streamed update (ipls_agg_update_gradient_chunked) ----
+// The front (ipls_agg.cpp) plans the call (flat_plan.hpp) and drives one stage
+// per involved shard through these: begin, then per received chunk slot / copy,
+// then landed; every stage of the call is committed by ONE dev_flat_commit, or
+// given up by dev_flat_abort.  Nothing here but the commit takes an engine lock.
+constexpr size_t kFlatPad = 16;   // bytes before and after the staged segment (k_update_flat's shifted loads)
+
+int dev_flat_begin(ipls_dev* h, Fmt fmt, int64_t seg, int64_t slot_elems, ipls_stage** st_out) {
+  if (!h || !st_out || seg < 0 || slot_elems < 1) return fail_nl(h, IPLS_E_INVAL, "bad argument");
+  *st_out = nullptr;
+  HIP_TRY_NL(h, dev_use(h->device));
+  const size_t esz = (size_t)fmt_size(fmt);
+  ipls_stage* st = nullptr;
+  if (int rc = stage_acquire(h, (size_t)seg * esz + 2 * kFlatPad, (size_t)slot_elems * esz, &st)) return rc;
+  // the fold that last read the device buffer runs before this call's copies overwrite it
+  for (int i = 0; i < st->n_copy && st->free_pending; ++i) {
+    const hipError_t e = hipStreamWaitEvent(st->copy[i], st->free_ev, 0);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      stage_release(h, st);
+      return fail_nl(h, IPLS_E_DEVICE, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
+    }
+  }
+  *st_out = st;
+  return IPLS_OK;
+}
+
+// The pinned slot chunk k of this stage is received into, free to be written.
+int dev_flat_slot(ipls_dev* h, ipls_stage* st, int64_t k, void** host) {
+  HIP_TRY_NL(h, dev_use(h->device));
+  PinnedSlot& sl = st->slot[k % st->n_slot];
+  if (int rc = stage_slot_free(h, sl)) return rc;   // the copy of chunk k - n_slot still reads this slot
+  *host = sl.host;
+  return IPLS_OK;
+}
+
+// Chunk k's H2D ranges (elements of the slot -> elements of the staged segment).
+int dev_flat_copy(ipls_dev* h, ipls_stage* st, int64_t k, Fmt fmt, const int64_t* src, const int64_t* dst,
+                  const int64_t* n, int n_copies) {
+  if (n_copies <= 0) return IPLS_OK;
+  HIP_TRY_NL(h, dev_use(h->device));
+  const size_t esz = (size_t)fmt_size(fmt);
+  PinnedSlot& sl = st->slot[k % st->n_slot];
+  hipStream_t cs = st->copy[k % st->n_copy];
+  char* d_in = (char*)st->d + kFlatPad;
+  for (int i = 0; i < n_copies; ++i) {
+    if (src[i] < 0 || dst[i] < 0 || n[i] < 0 || (size_t)(src[i] + n[i]) * esz > sl.cap ||
+        (size_t)(dst[i] + n[i]) * esz + 2 * kFlatPad > st->d_cap)
+      return fail_nl(h, IPLS_E_INVAL, "internal: a staged range outside its buffers");
+    HIP_TRY_NL(h, hipMemcpyAsync(d_in + (size_t)dst[i] * esz, (const char*)sl.host + (size_t)src[i] * esz,
+                                 (size_t)n[i] * esz, hipMemcpyHostToDevice, cs));
+    sl.pending = true;   // from the first queued copy on: the event below, or the abort's drain, clears it
+  }
+  HIP_TRY_NL(h, hipEventRecord(sl.ev, cs));
+  return IPLS_OK;
+}
+
+int dev_flat_landed(ipls_dev* h, ipls_stage* st) {
+  HIP_TRY_NL(h, dev_use(h->device));
+  for (int i = 0; i < st->n_copy; ++i) HIP_TRY_NL(h, hipEventRecord(st->landed[i], st->copy[i]));
+  return IPLS_OK;
+}
+
+// Give the stage up: the copies already queued finish before it is reused.
+void dev_flat_abort(ipls_dev* h, ipls_stage* st) {
+  if (!h || !st) return;
+  (void)dev_use(h->device);
+  for (int i = 0; i < st->n_copy; ++i) (void)hipStreamSynchronize(st->copy[i]);
+  (void)hipGetLastError();
+  for (auto& sl : st->slot) sl.pending = false;
+  stage_release(h, st);
+}
+
+template <class S, bool BE>
+static void launch_update_flat(hipStream_t st, dim3 grid, const FlatJob* jobs, const void* src) {
+  hipLaunchKernelGGL((k_update_flat<S, BE>), grid, dim3(kBlock), 0, st, jobs, (const typename S::elem*)src);
+}
+
+// The commit of one call: the engines' locks in the order given (the front
+// passes ascending shard index), ALL held at once; under them every shard
+// first folds its queued arrivals and makes its stream wait for the stage's
+// copies, then every shard gets its launch(es); then the locks go.  So the
+// gradient is one unit against every other call on those shards.  A failure
+// before the first launch leaves every accumulator and flag as it was.  The
+// stages are released (after a drain of their copy streams on failure).
+int dev_flat_commit(const flat_commit* c, int n, Fmt fmt) {
+  int rc = IPLS_OK;
+  for (int s = 0; s < n; ++s) c[s].h->mu.lock();
+  for (int s = 0; s < n && !rc; ++s) {
+    ipls_dev* h = c[s].h;
+    const hipError_t e0 = dev_use(h->device);
+    if (e0 != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(h, IPLS_E_DEVICE, "dev_use failed: %s", hipGetErrorString(e0));
+      break;
+    }
+    rc = flush_pending(h);   // earlier queued device buckets fold first
+    for (int i = 0; i < c[s].st->n_copy && !rc; ++i) {
+      const hipError_t e = hipStreamWaitEvent(h->stream, c[s].st->landed[i], 0);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(h, IPLS_E_DEVICE, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
+      }
+    }
+  }
+  const int64_t tile = fmt_trainer(fmt) ? flat_tile<FmtF32>() : flat_tile<FmtD64>();
+  for (int s = 0; s < n && !rc; ++s) {
+    ipls_dev* h = c[s].h;
+    rc = [&]() -> int {
+      HIP_TRY(h, dev_use(h->device));
+      const char* d_in = (const char*)c[s].st->d + kFlatPad;
+      const flat_job* fj = c[s].jobs;
+      for (int l = 0; l < c[s].n_launches; fj += c[s].launch_len[l], ++l) {
+        for (int j0 = 0; j0 < c[s].launch_len[l]; j0 += 65535) {   // gridDim.y
+          const int nj = std::min(65535, c[s].launch_len[l] - j0);
+          std::vector<FlatJob> jobs((size_t)nj);
+          int64_t maxL = 1;
+          bool all_vec = true, all_zero = true;
+          for (int j = 0; j < nj; ++j) {
+            const flat_job& f = fj[j0 + j];
+            if (f.q < 0 || f.q >= h->P || f.ncopy < 0 || f.ncopy > h->len[f.q] - 1 || f.lo < 0)
+              return fail(h, IPLS_E_INVAL, "internal: bad whole-gradient job");
+            FlatJob& o = jobs[(size_t)j];
+            o.lo = f.lo;
+            o.ncopy = f.ncopy;
+            o.L = h->len[f.q];
+            o.dst = (unsigned long long*)(h->arena + h->agg_off[f.q]);
+            o.zero = h->agg_zero[f.q];
+            maxL = std::max(maxL, o.L);
+            all_vec = all_vec && f.ncopy >= tile;
+            all_zero = all_zero && o.zero;
+          }
+          void* djobs = nullptr;
+          if (int r = upload_table(h, jobs.data(), jobs.size() * sizeof(FlatJob), &djobs)) return r;
+          const dim3 grid(blocks_for(maxL, tile), (unsigned)nj);
+          if (fmt == kFmtF64) launch_update_flat<FmtD64, false>(h->stream, grid, (const FlatJob*)djobs, d_in);
+          else if (fmt == kFmtBE) launch_update_flat<FmtD64, true>(h->stream, grid, (const FlatJob*)djobs, d_in);
+          else
+            with_narrow(fmt, [&](auto sfmt) {
+              launch_update_flat<decltype(sfmt), false>(h->stream, grid, (const FlatJob*)djobs, d_in);
+            });
+          HIP_TRY(h, hipGetLastError());
+          for (int j = 0; j < nj; ++j) h->agg_zero[fj[j0 + j].q] = 0;
+          h->last_launch = launch_info(IPLS_KERNEL_UPDATE_FLAT, 0, kBlock, kFlatR, all_vec ? 1 : 0, 0,
+                                       (int64_t)grid.x * grid.y, fmt == kFmtBE, false, all_zero ? kZero : kAccum);
+        }
+      }
+      return IPLS_OK;
+    }();
+  }
+  for (int s = 0; s < n; ++s) {
+    ipls_dev* h = c[s].h;
+    ipls_stage* st = c[s].st;
+    // whatever ran, nothing queued on the shard stream after this point reads `d`
+    if (dev_use(h->device) == hipSuccess && hipEventRecord(st->free_ev, h->stream) == hipSuccess) {
+      st->free_pending = true;
+    } else {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(h->stream);
+      st->free_pending = false;
+    }
+  }
+  for (int s = n - 1; s >= 0; --s) c[s].h->mu.unlock();
+  for (int s = 0; s < n; ++s) {
+    if (rc) {   // a shard stream may not have waited for the copies: drain them
+      (void)dev_use(c[s].h->device);
+      for (int i = 0; i < c[s].st->n_copy; ++i) (void)hipStreamSynchronize(c[s].st->copy[i]);
+      (void)hipGetLastError();
+      for (auto& sl : c[s].st->slot) sl.pending = false;
+    }
+    stage_release(c[s].h, c[s].st);
+  }
+  return rc;
+}
+
 // A stage's device snapshot (complete once st->ready fires) handed out in
 // pieces, with no engine lock held: piece k + 1 crosses PCIe into one pinned
 // slot on the stage's copy stream while the consumer has piece k from the

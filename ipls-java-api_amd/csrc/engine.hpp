@@ -74,6 +74,35 @@ int dev_accumulate_chunked(ipls_dev* h, int p, int target, int64_t n, int src_ki
                            ipls_chunk_source source, void* ctx);
 int dev_accumulate_chunked_narrow(ipls_dev* h, int p, int target, int64_t n, int src_kind, int64_t chunk,
                                   ipls_chunk_source source, void* ctx);
+// ---- ipls_agg_update_gradient_chunked: one stage per involved shard ----
+// The front plans the call (flat_plan.hpp) and feeds the stages in flat order:
+// dev_flat_begin (a stage whose device buffer holds `seg` elements of `fmt`
+// plus padding, pinned slots of slot_elems), then per source call
+// dev_flat_slot (the slot chunk k of THIS stage is received into, free to
+// write) and dev_flat_copy (its H2D ranges, in elements: slot -> segment),
+// dev_flat_landed after the stage's last chunk.  No engine lock is taken by
+// any of them.  dev_flat_commit then applies every stage of the call as one
+// unit (the engines' locks in the order given, all held at once; per shard
+// flush_pending, a wait for its copies, its launches of k_update_flat) and
+// releases the stages; dev_flat_abort drains and releases one instead.
+struct flat_job {
+  int q;                 // engine-local partition
+  int64_t lo, ncopy;     // first element in the staged segment, values copied
+};
+struct flat_commit {
+  ipls_dev* h;
+  ipls_stage* st;
+  const flat_job* jobs;      // the launches' jobs back to back
+  const int* launch_len;     // jobs per launch (no partition twice in one)
+  int n_launches;
+};
+int dev_flat_begin(ipls_dev* h, Fmt fmt, int64_t seg, int64_t slot_elems, ipls_stage** st);
+int dev_flat_slot(ipls_dev* h, ipls_stage* st, int64_t k, void** host);
+int dev_flat_copy(ipls_dev* h, ipls_stage* st, int64_t k, Fmt fmt, const int64_t* src, const int64_t* dst,
+                  const int64_t* n, int n_copies);
+int dev_flat_landed(ipls_dev* h, ipls_stage* st);
+void dev_flat_abort(ipls_dev* h, ipls_stage* st);
+int dev_flat_commit(const flat_commit* c, int n, Fmt fmt);
 int dev_finalize_chunked(ipls_dev* h, int p, int sum_kind, int64_t chunk, ipls_chunk_sink sink, void* ctx);
 int dev_get_partitions_chunked(ipls_dev* h, int64_t chunk, ipls_chunk_sink sink, void* ctx, bool wire);
 // the two phases of dev_get_partitions_chunked: the snapshot under the

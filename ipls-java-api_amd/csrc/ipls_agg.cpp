@@ -42,6 +42,7 @@
 
 #include "../../include/ipls_agg.h"
 #include "engine.hpp"
+#include "flat_plan.hpp"
 #include "java_hashmap.hpp"
 #include "javaser.hpp"
 #include "pubsub_host.hpp"
@@ -669,6 +670,102 @@ int ipls_agg_accumulate_chunked_narrow(ipls_agg* H, int p, int target, int64_t n
   int q;
   const int s = route(H, p, &q);
   return fwd(H, s, dev_accumulate_chunked_narrow(H->sh[s], q, target, n, src_kind, chunk, source, ctx));
+}
+
+// One whole flat gradient produced chunk by chunk, applied to every owned
+// partition at one instant (include/ipls_agg.h).  The plan is flat_plan.hpp's;
+// each involved shard gets a stage of its own, the stages are fed in flat order
+// on the calling thread (shard s's copies stay in flight while shard s + 1's
+// source calls run), and one dev_flat_commit applies them all.
+int ipls_agg_update_gradient_chunked(ipls_agg* H, int64_t n, int src_kind, const int32_t* owned, int n_owned,
+                                     int64_t chunk, ipls_chunk_source source, void* ctx) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (!source) return ferr(H, IPLS_E_INVAL, "null source");
+  if (src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE && !kind_trainer_host(src_kind))
+    return ferr(H, IPLS_E_INVAL, "a chunked gradient takes HOST_F64, HOST_BE, HOST_F32, HOST_F16 or HOST_BF16 values, "
+                "not kind %d", src_kind);
+  if (chunk < 2 || (chunk & 1)) return ferr(H, IPLS_E_INVAL, "chunk of %lld values: even and >= 2", (long long)chunk);
+  if (n < 0 || n_owned < 0 || (n_owned > 0 && !owned)) return ferr(H, IPLS_E_INVAL, "bad gradient length or owned list");
+  namespace fp = ipls::flatplan;
+  fp::Geometry g;
+  g.P = H->P;
+  g.chunk = H->chunk;
+  g.off = H->off;
+  g.len = H->len;
+  g.shard_lo = H->lo;
+  const fp::Plan pl = fp::make_plan(g, n, owned, n_owned, chunk);
+  if (pl.status == fp::kOverrun)
+    return ferr(H, IPLS_E_RANGE, "gradient vector of %lld values overruns partition %d "
+                "(ArrayIndexOutOfBounds, IPLS.java:1030)", (long long)n, pl.bad);
+  if (pl.status == fp::kBadPartition) return range_err(H, pl.bad);
+  if (pl.status != fp::kOk) return ferr(H, IPLS_E_INVAL, "bad argument");
+  if (pl.shards.empty()) return IPLS_OK;   // nothing owned: no source call
+
+  const Fmt fmt = kind_fmt(src_kind);
+  const int NS = (int)pl.shards.size();
+  int64_t slot_elems = 2;
+  for (const fp::Chunk& c : pl.chunks) slot_elems = std::max(slot_elems, c.n);
+  std::vector<ipls_stage*> st((size_t)NS, nullptr);
+  std::vector<int64_t> fed((size_t)NS, 0);       // chunks received into each stage so far
+  std::vector<char> landed((size_t)NS, 0);
+  auto dev = [&](int k) { return H->sh[(size_t)pl.shards[(size_t)k].shard]; };
+  auto give_up = [&](int rc) {
+    for (int k = 0; k < NS; ++k)
+      if (st[(size_t)k]) dev_flat_abort(dev(k), st[(size_t)k]);
+    return rc;
+  };
+  int rc = IPLS_OK;
+  // a stage is taken when the feed reaches it, and marked landed once the feed has passed its shard
+  auto begin = [&](int k) {
+    if (st[(size_t)k]) return IPLS_OK;
+    return fwd(H, 0, dev_flat_begin(dev(k), fmt, pl.shards[(size_t)k].seg, slot_elems, &st[(size_t)k]));
+  };
+  std::vector<int64_t> cs, cd, cn;
+  for (const fp::Chunk& c : pl.chunks) {
+    const int k = c.stage;
+    if ((rc = begin(k))) return give_up(rc);
+    for (int e = 0; e < k; ++e)   // the stages before this one have every chunk of theirs
+      if (st[(size_t)e] && !landed[(size_t)e]) {
+        if ((rc = fwd(H, 0, dev_flat_landed(dev(e), st[(size_t)e])))) return give_up(rc);
+        landed[(size_t)e] = 1;
+      }
+    void* host = nullptr;
+    const int64_t kk = fed[(size_t)k]++;
+    if ((rc = fwd(H, 0, dev_flat_slot(dev(k), st[(size_t)k], kk, &host)))) return give_up(rc);
+    if (source(ctx, host, c.off, c.n) != 0)   // no lock is held here
+      return give_up(ferr(H, IPLS_E_INVAL, "the chunk source stopped at offset %lld: nothing folded", (long long)c.off));
+    cs.clear(), cd.clear(), cn.clear();
+    for (int i = c.copy_lo; i < c.copy_hi; ++i) {
+      cs.push_back(pl.copies[(size_t)i].src);
+      cd.push_back(pl.copies[(size_t)i].dst);
+      cn.push_back(pl.copies[(size_t)i].n);
+    }
+    if ((rc = fwd(H, 0, dev_flat_copy(dev(k), st[(size_t)k], kk, fmt, cs.data(), cd.data(), cn.data(), (int)cs.size()))))
+      return give_up(rc);
+  }
+  for (int k = 0; k < NS; ++k) {   // shards the stream never reached (a short vector) and the last one fed
+    if ((rc = begin(k))) return give_up(rc);
+    if (!landed[(size_t)k]) {
+      if ((rc = fwd(H, 0, dev_flat_landed(dev(k), st[(size_t)k])))) return give_up(rc);
+      landed[(size_t)k] = 1;
+    }
+  }
+  // the commit: the involved shards' locks in ascending shard index, all held at once
+  std::vector<std::vector<flat_job>> jobs((size_t)NS);
+  std::vector<std::vector<int>> lens((size_t)NS);
+  std::vector<flat_commit> cm((size_t)NS);
+  for (int k = 0; k < NS; ++k) {
+    const fp::ShardPlan& sp = pl.shards[(size_t)k];
+    for (const auto& launch : sp.launches) {
+      lens[(size_t)k].push_back((int)launch.size());
+      for (const fp::Job& j : launch) jobs[(size_t)k].push_back(flat_job{j.p - H->lo[(size_t)sp.shard], j.lo, j.ncopy});
+    }
+    cm[(size_t)k] = flat_commit{dev(k), st[(size_t)k], jobs[(size_t)k].data(), lens[(size_t)k].data(),
+                                (int)lens[(size_t)k].size()};
+  }
+  H->last_shard.store(pl.shards.back().shard, std::memory_order_relaxed);
+  return fwd(H, 0, dev_flat_commit(cm.data(), NS, fmt));   // releases the stages
 }
 
 int ipls_agg_finalize_chunked(ipls_agg* H, int p, int sum_kind, int64_t chunk, ipls_chunk_sink sink, void* ctx) {

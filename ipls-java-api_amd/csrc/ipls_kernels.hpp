@@ -2346,4 +2346,206 @@ __global__ __launch_bounds__(64) void k_round_counts_narrow(const typename S::el
   if (lane == 0) cnts[q] = c + (d.rep ? __builtin_bit_cast(double, ld8(d.rep + e)) : 0.0);
 }
 
+// ---------------------------------------------------------------------------
+// k_update_flat: UpdateGradient's own accumulate (IPLS.java:1737-1743, k_split
+// MODE 1 / 2) over ALL owned partitions of a shard in one launch, from one
+// staged flat vector (ipls_agg_update_gradient_chunked).  blockIdx.y is the
+// job, blockIdx.x the tile of its partition:
+//   dst[i] = (zero ? +0.0 : dst[i]) + v,   v = (double)src[lo + i] for
+//   i < ncopy, 1.0 at i == ncopy (the count slot, generated here), 0.0 above
+//   (the add is still made: a -0.0 accumulator element becomes +0.0).
+// Tiling is aligned to the DESTINATION (accumulators are 256-B aligned): a
+// lane owns G consecutive elements at an aligned dst index -- 2 doubles (S =
+// FmtD64) or 4 elements (trainer formats) -- R = kFlatR groups kBlock groups
+// apart, so a tile is kBlock * G * R elements; all loads first, then the adds,
+// then 16-B stores (trainer formats through k_fold1_narrow's lane ^ 4
+// exchange, so a store instruction writes whole 128-B lines).
+// The source is only element-aligned: `src` (a kernel argument, 16-B aligned)
+// plus lo elements, and m = lo mod G is the job's residue against the lane's
+// load (16 B of doubles or floats, 8 B of 16-bit elements), uniform per job.
+//   m == 0: aligned vector loads, as k_split<VEC> / k_fold1_narrow.
+//   m != 0, SHIFT: the aligned vector load that holds the group's first
+//     element (it starts m elements early), completed with the first m
+//     elements of lane t + 1's load by __shfl_down; the wave's last lane loads
+//     its next vector itself.  The loads of a tile touch up to G - 1 elements
+//     before lo and after lo + ncopy: the stage is padded by 16 B at both
+//     ends, and between partitions those are the neighbour's bytes; they are
+//     loaded and never used.
+//   m != 0, !SHIFT: G naturally aligned element loads per group.
+// SHIFT defaults to the form that measured faster for the element width.
+// Tiles wholly inside [0, ncopy) take that body; the tile that holds ncopy and
+// everything after it go element by element.  The zero flag is a per-job
+// uniform branch.  BE_IN (doubles only): big-endian bytes, bswap in registers.
+// ---------------------------------------------------------------------------
+struct FlatJob {
+  int64_t lo;                 // first source element of the partition, from `src`
+  int64_t ncopy, L;
+  unsigned long long* dst;    // the accumulator (256-B aligned)
+  int64_t zero;               // logically +0.0: written without being read
+};
+struct FmtD64 {               // doubles as 64-bit words (native or big-endian)
+  typedef unsigned long long elem;
+};
+// Which form a non-zero residue takes, per element width, as measured
+// (tools/update_flat_sweep.hip): doubles are faster shifted,
+// the trainer formats with element loads.  Both forms are instantiated by the
+// sweep tool, which also compares their bits.
+#ifndef IPLS_FLAT_SHIFT
+#define IPLS_FLAT_SHIFT 1          // doubles: 1 shifted aligned loads, 0 element loads
+#endif
+#ifndef IPLS_FLAT_SHIFT_NARROW
+#define IPLS_FLAT_SHIFT_NARROW 0   // f32 / f16 / bf16: the same choice
+#endif
+constexpr int kFlatR = 4;
+template <class S>
+constexpr int64_t flat_tile() { return (int64_t)kBlock * (sizeof(typename S::elem) == 8 ? 2 : 4) * kFlatR; }
+template <class S>
+constexpr bool flat_shift() { return sizeof(typename S::elem) == 8 ? IPLS_FLAT_SHIFT != 0 : IPLS_FLAT_SHIFT_NARROW != 0; }
+
+template <class S, bool BE_IN, bool SHIFT = flat_shift<S>()>
+__global__ __launch_bounds__(kBlock) void k_update_flat(const FlatJob* __restrict__ jobs,
+                                                        const typename S::elem* __restrict__ src0) {
+  typedef typename S::elem T;
+  constexpr bool kWide = sizeof(T) == 8;
+  static_assert(kWide || !BE_IN, "only doubles come big-endian");
+  constexpr int R = kFlatR;
+  constexpr int64_t tile = flat_tile<S>();
+  const FlatJob j = jobs[blockIdx.y];
+  const int64_t base = (int64_t)blockIdx.x * tile;
+  if (base >= j.L) return;
+  const T* src = src0 + j.lo;
+  unsigned long long* dst = j.dst;
+  const bool zero = j.zero != 0;
+  const int tid = threadIdx.x;
+  const bool last = (tid & 63) == 63;   // no lane t + 1 in the wave
+  if (base + tile <= j.ncopy) {
+    // MODE 0: aligned loads; 1: shifted aligned loads; 2: element loads.  One body per mode, chosen by the
+    // job-uniform residue outside the loops, so each holds only its own registers.
+    if constexpr (kWide) {
+      auto body = [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        u2 sv[R], dv[R];
+        unsigned long long ex[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int64_t i = base + 2 * ((int64_t)r * kBlock + tid);
+          ex[r] = 0;
+          if constexpr (MODE == 0) {
+            sv[r] = __builtin_nontemporal_load((gcu2)(src + i));
+          } else if constexpr (MODE == 1) {
+            sv[r] = __builtin_nontemporal_load((gcu2)(src + i - 1));   // elements i - 1, i
+            if (last) ex[r] = ld8(src + i + 1);
+          } else {
+            sv[r].x = ld8(src + i);
+            sv[r].y = ld8(src + i + 1);
+          }
+          if (!zero) dv[r] = *(gcu2)(dst + i);
+          else dv[r] = u2{0, 0};
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int64_t i = base + 2 * ((int64_t)r * kBlock + tid);
+          u2 raw = sv[r];
+          if constexpr (MODE == 1) {
+            const unsigned long long own = sv[r].x, up = sv[r].y;
+            const unsigned long long nx = __shfl_down(own, 1);   // lane t + 1's element i + 1
+            raw.x = up;
+            raw.y = last ? ex[r] : nx;
+          }
+          const d2 x = decode2<BE_IN>(raw);
+          const d2 a = __builtin_bit_cast(d2, dv[r]);   // +0.0 when the accumulator is logically zero
+          *(gu2)(dst + i) = encode2<false>(d2{a.x + x.x, a.y + x.y});
+        }
+      };
+      if ((j.lo & 1) == 0) body(std::integral_constant<int, 0>{});
+      else body(std::integral_constant<int, SHIFT ? 1 : 2>{});
+    } else {
+      const int m = (int)(j.lo & 3);
+      typedef typename S::template Vec<4> V;
+      constexpr bool kF32 = sizeof(T) == 4;
+      auto body = [&](auto mode) {
+        constexpr int MODE = decltype(mode)::value;
+        V sv[R], nv[R];
+        typename S::raw el[R][4];
+        u2 t[R][2];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int64_t i = base + 4 * ((int64_t)r * kBlock + tid);
+          if constexpr (MODE == 0) {
+            sv[r] = S::template ldv<4>(src + i);
+          } else if constexpr (MODE == 1) {
+            sv[r] = S::template ldv<4>(src + i - m);                  // elements i - m .. i - m + 3
+            nv[r] = sv[r];
+            if (last) nv[r] = S::template ldv<4>(src + i - m + 4);
+          } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) el[r][c] = S::ldraw(src + i + c);
+          }
+          if (!zero) {
+            t[r][0] = ld16<false>(dst + i);
+            t[r][1] = ld16<false>(dst + i + 2);
+          } else {
+            t[r][0] = t[r][1] = u2{0, 0};
+          }
+        }
+        const bool hi = tid & 4;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          double v[4];
+          if constexpr (MODE == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = S::template get<4>(sv[r], c);
+          } else if constexpr (MODE == 1) {
+            if constexpr (kF32) {
+              const float o0 = sv[r].x, o1 = sv[r].y, o2 = sv[r].z, o3 = sv[r].w;
+              float n0 = __shfl_down(o0, 1), n1 = __shfl_down(o1, 1), n2 = __shfl_down(o2, 1);
+              if (last) n0 = nv[r].x, n1 = nv[r].y, n2 = nv[r].z;
+              const float s0 = m == 1 ? o1 : m == 2 ? o2 : o3;
+              const float s1 = m == 1 ? o2 : m == 2 ? o3 : n0;
+              const float s2 = m == 1 ? o3 : m == 2 ? n0 : n1;
+              const float s3 = m == 1 ? n0 : m == 2 ? n1 : n2;
+              v[0] = (double)s0, v[1] = (double)s1, v[2] = (double)s2, v[3] = (double)s3;
+            } else {
+              const unsigned long long own = ((unsigned long long)sv[r].w[1] << 32) | sv[r].w[0];
+              unsigned long long nx = __shfl_down(own, 1);
+              if (last) nx = ((unsigned long long)nv[r].w[1] << 32) | nv[r].w[0];
+              const unsigned long long sh = (own >> (16 * m)) | (nx << (64 - 16 * m));   // m in 1..3
+              V s;
+              s.w[0] = (unsigned)sh, s.w[1] = (unsigned)(sh >> 32);
+#pragma unroll
+              for (int c = 0; c < 4; ++c) v[c] = S::template get<4>(s, c);
+            }
+          } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = S::widen(el[r][c]);
+          }
+          const d2 x = __builtin_bit_cast(d2, t[r][0]), y = __builtin_bit_cast(d2, t[r][1]);
+          const double a0 = x.x + v[0], a1 = x.y + v[1], a2 = y.x + v[2], a3 = y.y + v[3];
+          // k_fold1_narrow's stores: lanes 8k..8k+3 own one 128-B line of sums, 8k+4..8k+7 the next
+          const int64_t o = base + 4 * ((int64_t)r * kBlock + tid);
+          const d2 own = d2{a0, a1};
+          const d2 got = d2{__shfl_xor(a2, 4), __shfl_xor(a3, 4)};
+          __builtin_nontemporal_store(encode2<false>(hi ? got : own), (gu2)(dst + (hi ? o - 14 : o)));
+          __builtin_nontemporal_store(encode2<false>(hi ? own : got), (gu2)(dst + (hi ? o : o + 18)));
+        }
+      };
+      if (m == 0) body(std::integral_constant<int, 0>{});
+      else body(std::integral_constant<int, SHIFT ? 1 : 2>{});
+    }
+    return;
+  }
+  const int64_t end = base + tile < j.L ? base + tile : j.L;
+  for (int64_t i = base + tid; i < end; i += kBlock) {
+    double v;
+    if (i < j.ncopy) {
+      if constexpr (kWide) v = decode1<BE_IN>(ld8(src + i));
+      else v = S::widen(S::ldraw(src + i));
+    } else {
+      v = i == j.ncopy ? 1.0 : 0.0;
+    }
+    const double a = zero ? 0.0 : __builtin_bit_cast(double, ld8(dst + i));
+    st8(dst + i, __builtin_bit_cast(unsigned long long, a + v));
+  }
+}
+
 }  // namespace ipls

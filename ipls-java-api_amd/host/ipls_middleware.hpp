@@ -121,9 +121,12 @@ class MiddlewareServer {
   };
 
   // opts: Middleware.parse_arguments' PeerData (-pa, -n, device ...);
-  // io_timeout_ms bounds each blocking socket read/write of a connection
-  explicit MiddlewareServer(PeerData opts, int64_t chunk = 1 << 19, int io_timeout_ms = 60000)
-      : opts_(std::move(opts)), chunk_(chunk), io_timeout_ms_(io_timeout_ms) {}
+  // io_timeout_ms bounds each blocking socket read/write of a connection;
+  // unit_updates: task 2 is ONE ipls_agg_update_gradient_chunked call over the
+  // whole Auth_List instead of one chunked fold per partition (see task2)
+  explicit MiddlewareServer(PeerData opts, int64_t chunk = 1 << 19, int io_timeout_ms = 60000,
+                            bool unit_updates = false)
+      : opts_(std::move(opts)), chunk_(chunk), io_timeout_ms_(io_timeout_ms), unit_updates_(unit_updates) {}
   ~MiddlewareServer() {
     if (lfd_ >= 0) ::close(lfd_);
   }
@@ -191,6 +194,7 @@ class MiddlewareServer {
   const Stats& stats() const { return stats_; }
   const Init& init() const { return init_; }
   IPLS* ipls() { return ipls_.get(); }
+  int pending() const { return pending_; }   // updates of the open round
 
  private:
   static constexpr uint8_t kAck[2] = {0x00, 0x41};   // writeChar('A')
@@ -242,9 +246,22 @@ class MiddlewareServer {
       }
       return 0;
     };
-    for (int32_t p : ipls_->Auth_List) {
-      Src s{fd, ipls_->partition_length(p)};
-      check(ipls_agg_accumulate_chunked(h, p, IPLS_TGT_AGG, s.L, IPLS_HOST_BE, chunk_, source, &s), h);
+    if (unit_updates_) {
+      // the whole update as one unit: the stream goes straight into the ring,
+      // the count slots are the kernel's, and a client that stops mid-stream
+      // leaves every partition (and pending_) as it was -- the reference reads
+      // the whole stream before UpdateModel takes PeerData.mtx
+      // (Middleware.java:156-160, 224, 246)
+      auto whole = [](void* ctx, void* dst, int64_t, int64_t n) -> int {
+        return recv_exact(*(const int*)ctx, dst, (size_t)n * 8) ? 0 : 1;
+      };
+      check(ipls_agg_update_gradient_chunked(h, init_.model_size, IPLS_HOST_BE, ipls_->Auth_List.data(),
+                                             (int)ipls_->Auth_List.size(), chunk_, whole, &fd), h);
+    } else {
+      for (int32_t p : ipls_->Auth_List) {
+        Src s{fd, ipls_->partition_length(p)};
+        check(ipls_agg_accumulate_chunked(h, p, IPLS_TGT_AGG, s.L, IPLS_HOST_BE, chunk_, source, &s), h);
+      }
     }
     if (++pending_ >= opts_.Min_Members) {   // the loopback round closes after -n updates
       check(ipls_agg_finalize(h, IPLS_ALL_PARTITIONS, nullptr, IPLS_HOST_BE, nullptr), h);
@@ -273,6 +290,7 @@ class MiddlewareServer {
   PeerData opts_;
   int64_t chunk_;
   int io_timeout_ms_;
+  bool unit_updates_ = false;
   int lfd_ = -1;
   std::unique_ptr<IPLS> ipls_;
   Init init_;

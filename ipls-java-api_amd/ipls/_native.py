@@ -32,6 +32,7 @@ KERNEL_REDUCE_F32 = 5
 KERNEL_REDUCE_H16 = 6
 KERNEL_ROUND_F32, KERNEL_ROUND_H16 = 7, 8
 KERNEL_FOLD1_F32, KERNEL_FOLD1_H16 = 9, 10   # k_fold1_narrow: one trainer-format arrival
+KERNEL_UPDATE_FLAT = 11                      # k_update_flat: one whole streamed gradient (update_gradient_chunked)
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -120,6 +121,7 @@ SIGNATURES = {
     "ipls_agg_get_partitions_wire_chunked": (_i, [_vp, _i64, _vp, _vp]),   # sink: a CHUNK_SINK instance
     "ipls_agg_accumulate_chunked": (_i, [_vp, _i, _i, _i64, _i, _i64, _vp, _vp]),   # source: a CHUNK_SOURCE
     "ipls_agg_accumulate_chunked_narrow": (_i, [_vp, _i, _i, _i64, _i, _i64, _vp, _vp]),   # source: a CHUNK_SOURCE
+    "ipls_agg_update_gradient_chunked": (_i, [_vp, _i64, _i, _vp, _i, _i64, _vp, _vp]),   # owned: int32[], source: a CHUNK_SOURCE
     "ipls_agg_get_partitions_chunked_narrow": (_i, [_vp, _i, _i64, _vp, _vp]),   # sink: a BYTE_SINK instance
     "ipls_agg_finalize_chunked": (_i, [_vp, _i, _i, _i64, _vp, _vp]),   # sink: a CHUNK_SINK instance
     "ipls_agg_wait": (_i, [_vp, _u64]),

@@ -464,6 +464,33 @@ class Aggregator:
         _reraise(caught)
         self._chk(rc)
 
+    def UpdateGradientChunked(self, n: int, source, auth_list, *, big_endian: bool = True, dtype=None,
+                              chunk: int = 1 << 19):
+        """UpdateGradient (IPLS.java:1708-1743) of one whole flat gradient
+        of ``n`` values that the caller produces chunk by chunk, as ONE library
+        call (ipls_agg_update_gradient_chunked): the bits of UpdateGradient on
+        the same vector, applied to every partition of ``auth_list`` at one
+        instant once the last chunk has landed, or not at all.  ``source(dst,
+        offset, count)`` writes the vector's values [offset, offset + count)
+        at the address ``dst`` (the library's pinned ring) and returns True;
+        False stops the call with every partition untouched.  It is called for
+        consecutive chunks of the whole vector, also where no listed partition
+        has values (a socket source must consume the stream).  ``dtype`` and
+        ``big_endian`` as in UpdateChunked: 8*count big-endian bytes by
+        default, native doubles with ``big_endian=False``, or 4*count / 2*count
+        bytes of ``np.float32`` / ``np.float16`` / ``"bf16"``."""
+        kind = (N.HOST_BE if big_endian else N.HOST_F64) if dtype is None else _HOST_KIND[_chunked_dtype(dtype)]
+        owned = np.ascontiguousarray(np.asarray(list(auth_list), dtype=np.int32))
+        caught = []
+
+        @N.CHUNK_SOURCE
+        def cb(ctx, dst, off, cnt):
+            return _callback(caught, source, dst, off, cnt)
+        rc = self._lib.ipls_agg_update_gradient_chunked(
+            self._h, n, kind, owned.ctypes.data_as(ctypes.c_void_p), len(owned), chunk, cb, None)
+        _reraise(caught)
+        self._chk(rc)
+
     def GetPartitionsChunked(self, sink, *, wire: bool = False, chunk: int = 1 << 19, dtype=None):
         """GetPartitions (IPLS.java:1159-1174) handed to ``sink(ptr, offset,
         count)`` chunk by chunk in model order (ipls_agg_get_partitions_chunked,

@@ -183,6 +183,7 @@ class LoopbackAggregator:
         self._staging = None   # whole-payload pinned staging of update_model / get_partitions_wire, on first use
         self.pending = 0
         self.rounds = 0
+        self.unit_chunk = 1 << 19   # values per source call of update_from_socket(unit=True)
         self.lock = threading.Lock()
         # host seconds inside the aggregator per task (the rest of a task is the socket)
         self.stats = {"updates": 0, "update_s": 0.0, "replies": 0, "reply_s": 0.0}
@@ -214,7 +215,7 @@ class LoopbackAggregator:
             self.pending = 0
             self.rounds += 1
 
-    def update_from_socket(self, sock: socket.socket):
+    def update_from_socket(self, sock: socket.socket, unit: bool = False):
         """Task 2 streamed off the socket (Deserialize, Middleware.java:156-160,
         then UpdateGradient, IPLS.java:1737-1743): partition p's slice of the
         update -- the next L_p - 1 big-endian doubles of the stream, then its
@@ -228,8 +229,31 @@ class LoopbackAggregator:
         server's own tasks and round count only).  Same bits as update_model on the whole
         payload.  A connection that ends mid-update raises (Java's
         EOFException ends the Middleware, Middleware.java:262-265), with the
-        partitions received before it already folded."""
+        partitions received before it already folded.
+
+        ``unit=True``: the whole task is ONE ipls_agg_update_gradient_chunked
+        call over every partition instead -- the stream is received chunk by
+        chunk into the ring as above, and the update takes effect in all
+        partitions at one instant after its last byte, or (a client that stalls
+        or disconnects mid-stream) in none: every partition, count slot and
+        ``pending`` stay as they were, so a retry folds once.  The reference
+        reads the whole stream before UpdateModel takes PeerData.mtx
+        (Middleware.java:156-160, 224, 246).  Same bits."""
         one = struct.pack(">d", 1.0)
+        if unit:
+            with self.lock:
+                t0 = time.perf_counter()
+
+                def whole(dst, off, n):
+                    _recv_exact(sock, 8 * n, (ctypes.c_char * (8 * n)).from_address(dst))
+                    return True
+                self.agg.UpdateGradientChunked(self.model_size, whole, range(self.opts.partitions),
+                                               chunk=self.unit_chunk)
+                self._close_round_if_due()
+                self.agg.sync()
+                self.stats["update_s"] += time.perf_counter() - t0
+                self.stats["updates"] += 1
+            return
         with self.lock:
             t0 = time.perf_counter()
             for p in range(self.opts.partitions):
@@ -283,7 +307,7 @@ class LoopbackAggregator:
 
 def serve(opts: Options, max_connections: int | None = None, device: int = 0, initial_model=None,
           ready: threading.Event | None = None, host: str = "127.0.0.1", on_listen=None, on_daemon=None,
-          io_timeout: float | None = 60.0, on_error=None):
+          io_timeout: float | None = 60.0, on_error=None, unit_updates: bool = False):
     """Middleware.main (Middleware.java:212-268): one connection per task.
     ``opts.port`` 0 binds a free port; ``on_listen(port)`` is told which, and
     ``on_daemon(aggregator)`` gets the LoopbackAggregator task 1 creates.
@@ -300,7 +324,9 @@ def serve(opts: Options, max_connections: int | None = None, device: int = 0, in
     (:262-265); a server of many peers should not be ended by one bad one.
     A task 2 that fails mid-stream leaves the partitions whose slices fully
     arrived folded, the rest untouched (each partition is one
-    all-or-nothing call)."""
+    all-or-nothing call).  ``unit_updates=True`` makes task 2 one
+    whole-gradient call instead (update_from_socket(unit=True)): a failed
+    task 2 then leaves every partition untouched."""
     srv = socket.socket()
     srv.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
     srv.bind((host, opts.port))
@@ -329,7 +355,7 @@ def serve(opts: Options, max_connections: int | None = None, device: int = 0, in
                     elif task in (2, 3) and daemon is None:
                         raise MiddlewareTaskError(f"task {task} before task 1")
                     elif task == 2:
-                        daemon.update_from_socket(conn)
+                        daemon.update_from_socket(conn, unit=unit_updates)
                         conn.sendall(ACK)
                     elif task == 3:
                         daemon.reply_to_socket(conn)
