@@ -15,7 +15,9 @@ workload (tests/golden/golden.json "full", config D = 64 x 4M x 32 in full).
 Division of labour: production sizes and checksums here; the seams of the
 same shapes (lengths around a tile, K across the peer groups, special values,
 guard bands, ragged and tiny partitions, every launch record) in
-tests/test_gpu_wide_small.py, at the smallest batches that reach them.
+tests/test_gpu_wide_small.py, at the smallest batches that reach them; the
+seams of the unfused round (k_finalize, k_divide at every output head, the
+big-endian outputs) in tests/test_gpu_unfused_round.py.
 References: MyIPFSClass.java:444-455 (GetParameters BE decode),
 :105-116 (update_file BE encode), Decentralized_Storage_Receiver.java:239-257
 (FIRST-start merge), Updater.java:115-117 (the fold), IPLS.java:1248-1274 and
