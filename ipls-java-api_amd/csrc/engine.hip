@@ -30,6 +30,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ipls_agg.h"
@@ -37,8 +38,10 @@
 #include "javaser.hpp"
 #include "engine.hpp"
 #include "pubsub_host.hpp"
+#include "reduce_plan.hpp"
 
 using namespace ipls;
+using namespace ipls::reduceplan;
 
 namespace {
 
@@ -556,286 +559,25 @@ static void launch_bswap(hipStream_t st, const unsigned long long* in, unsigned 
   else hipLaunchKernelGGL(k_bswap64<false>, ew_grid(n, false, 4096), dim3(kBlock), 0, st, in, out, n);
 }
 
-// ---- kernel dispatch: k_reduce ----
-// Three shapes (tools/reduce_sweep.hip, profiles/r01/sweep*.txt), the first
-// whose tiles fill the 256 CUs (fill()):
-//  * big: 1024-lane workgroups, 1 peer in flight x 16 x 16 B per lane, i.e.
-//    each CU streams one 256 KiB contiguous chunk of one bucket at a time
-//    (fewer, longer DRAM streams): 85-89 % of 8 TB/s on config C over every
-//    bucket layout tried, vs 80-86 % for 256-lane / 64 KiB blocks;
-//  * mid: the same per-lane work on 256-lane workgroups (64 KiB chunks), for
-//    batches of one or a few partitions: 1 x 4M x 32 at 86.2 % vs 72.7 % for
-//    the small shape and 55.8 % for the big one on 128 CUs
-//    (profiles/r01/sweep_few_partitions.txt);
-//  * small: 256 lanes, 8 peers in flight x 16 B per lane, partition-major --
-//    enough blocks for short partitions (ETHModel's 3 x 147,872).
-constexpr int kBigG = 1, kBigMap = 0, kBigBS = 1024, kMidBS = 256;
-constexpr int kSmallG = 8, kSmallR = 1, kSmallMap = 0;
-// A tile count fills the chip when it is at least two waves of 256 CUs, or
-// one or more waves with at most a fifth of the last one idle.
-inline bool fill(int64_t tiles) {
-  if (tiles >= 512) return true;
-  if (tiles < 256) return false;
-  const int64_t waves = (tiles + 255) / 256;
-  return tiles * 5 >= waves * 256 * 4;
+// ---- runtime flags -> template arguments ----
+// Each helper calls f with a value whose type carries the flag as a constant
+// (decltype(x)::value; a format is the type itself), so a launch site names
+// the combinations it instantiates.  The lambdas only launch.
+template <class F> auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> auto with_start(int start, F&& f) {
+  return start == kZero ? f(Int<kZero>{}) : start == kFirst ? f(Int<kFirst>{}) : f(Int<kAccum>{});
 }
-// 16 x 16 B per lane in the 128-VGPR budget of a 1024-lane workgroup:
-// native doubles 126 VGPRs; big-endian input 110 with the SEQ schedule of
-// reduce_tiles (hipcc's own schedule hoisted the loads around the bswap and
-// spilled 184 B).  The ACCUM start keeps 8 (at 16 it still spills around
-// the loop -- checked with -Rpass-analysis=kernel-resource-usage).
-// IPLS_BE_BIG_R / IPLS_BE_SEQF rebuild the big-endian big shape with another
-// schedule for same-process A/B runs (make -C ipls-java-api_amd variants,
-// bench.py --be-schedule-ab); the shipped library uses the defaults.
-#ifndef IPLS_BE_BIG_R
-#define IPLS_BE_BIG_R 16
-#endif
-#ifndef IPLS_BE_SEQF
-#define IPLS_BE_SEQF 3
-#endif
-template <bool BE_IN, int START, bool FIN = false>
-constexpr int big_r() { return START != kAccum ? (BE_IN ? IPLS_BE_BIG_R : 16) : 8; }
-// SEQ schedule of the big shape (0 = hipcc's own): big-endian input at R = 16
-// loads, decodes and adds a peer's vectors three at a time with a fence after
-// each group (SEQF = 3; 118 VGPRs, no spills).  Round 2 swept fence periods
-// 1-8 with and without a free tail in one process (profiles/r02/s3/
-// sweep_be_tail{1,2}*.txt): 3 beats round 1's every-2-with-the-last-4-free
-// (SEQF = 42) by 0.7-1.6 points on C's and D's shapes, BE in and in + out;
-// periods >= 5, a free tail on period 3, and period 1 are all slower.
-template <bool BE_IN, int START>
-constexpr int big_seqf() { return (BE_IN && big_r<BE_IN, START>() > 8) ? IPLS_BE_SEQF : 0; }
-// Block order of the big shape over whole tiles: partition-major (map 0),
-// except big-endian input on grids of at most 4096 tiles, which runs
-// XCD-chunked (map 2: each XCD walks one contiguous eighth of the work).  With
-// SEQF = 3, map 2 measured +2 to +3.6 points at 2-4 partitions of 4M x 32,
-// +0.2 to +0.6 at 16, and -3.6 at 64 (config D, 8192 tiles); native doubles
-// gain nothing from it at 16 (profiles/r02/s3/sweep_be_map.txt,
-// sweep_map_fewp.txt) and run the half shape below on short grids.
-template <bool BE_IN>
-inline int big_map(int64_t tiles) { return (BE_IN && tiles <= 4096) ? 2 : kBigMap; }
-// The half shape (round 3): ZERO/FIRST start, batches of fewer than 4
-// rounds of big tiles on 256 CUs (fewer than 1024 whole big tiles: one to
-// seven partitions of 4M, config B), and larger grids that the big tiles
-// would leave partly idle in their last round (below).  512-lane workgroups at R = 16 -- 128
-// KiB of a bucket per block, one workgroup per CU, no spills, every load of a
-// peer's chunk in flight: native doubles at 164 VGPRs, big-endian input on
-// hipcc's own schedule at 172 (the 256-VGPR budget of 512 lanes needs no SEQ
-// fences).  Same process, same buckets (profiles/r03/e/sweep_fewp.txt,
-// r03/f/sweep_512_*.txt, r03/h/sweep_fewp_be.txt): native 1/2/3/5/7
-// partitions of 4M x 32 at 87.1/83.2/89.8/89.5/89.1 % against 56.2/80.5/
-// 74.9/80.7/82.7 % for the big shape (whose 128 tiles per partition leave
-// half a round idle at odd counts) and 87.4/70.1/85.2/78.5/81.0 % for mid;
-// big-endian in + out 88.2/87.8/87.0/86.0/85.0 % against 84.3 (mid)/82.7/
-// 84.5 (mid)/79.6/82.9 % for what shipped; config B 80.2-82.3 % against
-// 78.7-81.8 %.  At config C (2048 big tiles) the big shape stays ahead
-// (87.1-87.8 vs 85.0-87.1 %), at F they tie, at D (BE) big SEQF = 3 wins.
-// Both counts are of WHOLE tiles: a partial last tile (map 3) is scheduled
-// first and runs beside the first round, so 4M + 3 doubles is one round of
-// 256 half tiles, not 257.
-constexpr int kHalfBS = 512, kHalfR = 16;
-// The fused round (k_round, 166 VGPRs native / 174 big-endian at 512 lanes,
-// no spills) takes the half shape on the same rule: same process, same
-// buckets against its big/mid shapes (tools/half_round_probe.py,
-// profiles/r03/i/half_round_probe.jsonl): 1/2/3/5 partitions of 4M x 32 at
-// 85.4/81.2/80.8/81.0 % vs 84.5/79.0/78.1/74.2 %, 3 x 4M big-endian 80.2 vs
-// 74.3 %, config B's shape 71.9 vs 72.8 %.  IPLS_HALF_ROUND=0 builds the
-// fused round without it (the A/B variant, make variants).
-#ifndef IPLS_HALF_ROUND
-#define IPLS_HALF_ROUND 1
-#endif
-// ACCUM (the fold reads its target too) on fewer than 1024 big R = 16
-// tiles: the half shape at R = 16 (202 VGPRs native, 204 big-endian, no
-// spills) instead of the big R = 8 tiles of the same size.  Same process
-// (profiles/r03/k/sweep_accum.txt, r03/l/sweep_accum2*.txt): 1/2/3/5
-// partitions of 4M x 32 at 83.9/82.7/85.3/84.9 % vs 81.0/80.9/82.3/82.5 %,
-// big-endian 1/3 at 81.8/82.9 vs 79.2/81.4 %; at 16/32/64 partitions the two
-// tie (82.3/79.9/81.6 vs 81.8/80.2/81.2 %), which the big R = 8 tiles keep.
-// The fused round's ACCUM start (AGG already holds arrivals) keeps big/mid.
-#ifndef IPLS_HALF_ACCUM
-#define IPLS_HALF_ACCUM 1
-#endif
-// Past 4 rounds the half shape also takes grids whose big tiles leave part
-// of the last round idle while its own tiles do not (with L = 4M: 9, 11, 13,
-// 15 partitions; profiles/r03/k/sweep_midp.txt: 9 x 4M 87.3-87.5 vs 82.8-83.0 %,
-// 13 x 4M 84.3-84.4 vs 83.4-83.5 %), and leaves whole rounds to the big shape
-// (8, 10, 12 x 4M: big ahead by 0-0.8 points).
-inline double round_eff(int64_t tiles) {   // busy fraction of the rounds of 256 one-workgroup CUs
-  const int64_t r = (tiles + 255) / 256;
-  return r > 0 ? (double)tiles / (double)(r * 256) : 0.0;
+// ZERO or ACCUM only: the fused rounds (AGG is never FIRST-started) and k_fold1_narrow
+template <class F> auto with_start_za(int start, F&& f) { return start == kZero ? f(Int<kZero>{}) : f(Int<kAccum>{}); }
+// be_in x be_out x start: the flags of a fold over doubles
+template <class F> auto with_fold(bool be_in, bool be_out, int start, F&& f) {
+  return with_bool(be_in, [&](auto bi) {
+    return with_bool(be_out, [&](auto bo) { return with_start(start, [&](auto s) { return f(bi, bo, s); }); });
+  });
 }
-// The big tiles counted are the R = 16 ones (32768 doubles) for every start
-// mode: ACCUM's big shape runs R = 8 tiles the size of a half tile.
-// IPLS_HALF_ALWAYS=1 (A/B builds only) sends every grid that fills to it.
-#ifndef IPLS_HALF_ALWAYS
-#define IPLS_HALF_ALWAYS 0
-#endif
-inline bool use_half(int64_t maxL, int n_parts, int64_t half_tile) {
-  const int64_t tb = (maxL / ((int64_t)kBigBS * 2 * 16)) * n_parts, th = (maxL / half_tile) * n_parts;
-  return fill(th) && (IPLS_HALF_ALWAYS || tb < 1024 || round_eff(th) > round_eff(tb) + 0.06);
-}
-// The mid shape (256 lanes, one or two partitions: per-partition flushes, the
-// storage merge of one partition's files) with big-endian input runs 8
-// vectors per lane on hipcc's own schedule (100 VGPRs, no spills): one
-// partition of 4M x 32 peers at 83-86 % against 55-64 % for the big shape's
-// R = 16 SEQ schedules at 256 lanes (profiles/r02/s3/sweep_be_p1.txt, BE in
-// and BE in + out, two processes each).  Native doubles keep R = 16 (86-88 %).
-template <bool BE_IN, int START>
-constexpr int mid_r() { return BE_IN ? 8 : big_r<BE_IN, START>(); }
-template <bool BE_IN, int START>
-constexpr int mid_seqf() { return mid_r<BE_IN, START>() > 8 ? big_seqf<BE_IN, START>() : 0; }
-
-// C-ABI start mode -> kernel template start
-int kstart(int start_mode) {
-  return start_mode == IPLS_START_ZERO ? kZero : start_mode == IPLS_START_FIRST ? kFirst : kAccum;
-}
-
-// What a fold launch ran (ipls_agg_last_launch): tests assert that a case
-// reaches the kernel shape it was written for.
-ipls_launch_info launch_info(int kernel, int shape, int block, int r, int seqf, int map, int64_t grid, bool be_in,
-                             bool be_out, int start) {
-  ipls_launch_info li{};
-  li.kernel = kernel;
-  li.shape = shape;
-  li.block = block;
-  li.vectors = r;
-  li.seqf = seqf;
-  li.map = map;
-  li.grid = grid;
-  li.be_in = be_in;
-  li.be_out = be_out;
-  li.start = start == kZero ? IPLS_START_ZERO : start == kFirst ? IPLS_START_FIRST : IPLS_START_ACCUM;
-  return li;
-}
-
-template <bool BE_IN, bool BE_OUT, int START, bool FIN = false>
-ipls_launch_info launch_reduce_v(int64_t maxL, int n_parts, hipStream_t st, const unsigned long long* const* bufs,
-                                 const PartDesc* parts, int k, int secure = 0, const double* cnts = nullptr) {
-  constexpr int R = big_r<BE_IN, START, FIN>();
-  constexpr int RM = mid_r<BE_IN, START>();
-  constexpr int KER = FIN ? IPLS_KERNEL_ROUND : IPLS_KERNEL_REDUCE;
-  const int64_t big_tile = (int64_t)kBigBS * 2 * R;
-  const int64_t big_tpp = (maxL + big_tile - 1) / big_tile;
-  const int64_t mid_tile = (int64_t)kMidBS * 2 * RM;
-  const int64_t mid_tpp = (maxL + mid_tile - 1) / mid_tile;
-  if constexpr ((!FIN || IPLS_HALF_ROUND) && (START != kAccum || (IPLS_HALF_ACCUM && !FIN))) {
-    const int64_t half_tile = (int64_t)kHalfBS * 2 * kHalfR;
-    const int64_t half_tpp = (maxL + half_tile - 1) / half_tile;
-    if (use_half(maxL, n_parts, half_tile)) {
-      const bool partial = half_tpp > 1 && maxL % half_tile != 0;
-      const dim3 grid((unsigned)(half_tpp * n_parts));
-#define HALF(MAP)                                                                                         \
-      do {                                                                                                \
-        if constexpr (FIN)                                                                                \
-          hipLaunchKernelGGL((k_round<BE_IN, START, kBigG, kHalfR, MAP, kHalfBS, 0>), grid, dim3(kHalfBS), \
-                             0, st, bufs, parts, k, (int)half_tpp, n_parts, secure, cnts);                \
-        else                                                                                              \
-          hipLaunchKernelGGL((k_reduce<BE_IN, BE_OUT, START, kBigG, kHalfR, true, MAP, kHalfBS>), grid,   \
-                             dim3(kHalfBS), 0, st, bufs, parts, k, (int)half_tpp, n_parts);               \
-      } while (0)
-      if (partial) HALF(3);
-      else HALF(kBigMap);
-#undef HALF
-      return launch_info(KER, IPLS_SHAPE_HALF, kHalfBS, kHalfR, 0, partial ? 3 : kBigMap, grid.x, BE_IN, BE_OUT,
-                         START);
-    }
-  }
-  if (fill(big_tpp * n_parts)) {
-    // partial last tiles are scheduled first (map 3, ipls_kernels.hpp map_block)
-    const bool partial = big_tpp > 1 && maxL % big_tile != 0;
-    const int map = partial ? 3 : big_map<BE_IN>(big_tpp * n_parts);
-    const dim3 grid((unsigned)grid_blocks(map, big_tpp * n_parts));
-#define BIG(MAP)                                                                                          \
-    do {                                                                                                  \
-      if constexpr (FIN)                                                                                  \
-        hipLaunchKernelGGL((k_round<BE_IN, START, kBigG, R, MAP, kBigBS, big_seqf<BE_IN, START>()>), grid, \
-                           dim3(kBigBS), 0, st, bufs, parts, k, (int)big_tpp, n_parts, secure, cnts);     \
-      else                                                                                                \
-        hipLaunchKernelGGL((k_reduce<BE_IN, BE_OUT, START, kBigG, R, true, MAP, kBigBS,                   \
-                                     big_seqf<BE_IN, START>()>),                                          \
-                           grid, dim3(kBigBS), 0, st, bufs, parts, k, (int)big_tpp, n_parts);             \
-    } while (0)
-    if (map == 3) BIG(3);
-    else if (map == 2) BIG(2);
-    else BIG(kBigMap);
-#undef BIG
-    return launch_info(KER, IPLS_SHAPE_BIG, kBigBS, R, big_seqf<BE_IN, START>(), map, grid.x, BE_IN, BE_OUT, START);
-  } else if (fill(mid_tpp * n_parts)) {
-    const dim3 grid((unsigned)grid_blocks(kBigMap, mid_tpp * n_parts));
-    const bool partial = mid_tpp > 1 && maxL % mid_tile != 0;
-#define MID(MAP)                                                                                          \
-    do {                                                                                                  \
-      if constexpr (FIN)                                                                                  \
-        hipLaunchKernelGGL((k_round<BE_IN, START, kBigG, RM, MAP, kMidBS, mid_seqf<BE_IN, START>()>), grid, \
-                           dim3(kMidBS), 0, st, bufs, parts, k, (int)mid_tpp, n_parts, secure, cnts);     \
-      else                                                                                                \
-        hipLaunchKernelGGL((k_reduce<BE_IN, BE_OUT, START, kBigG, RM, true, MAP, kMidBS,                  \
-                                     mid_seqf<BE_IN, START>()>),                                          \
-                           grid, dim3(kMidBS), 0, st, bufs, parts, k, (int)mid_tpp, n_parts);             \
-    } while (0)
-    if (partial) MID(3);
-    else MID(kBigMap);
-#undef MID
-    return launch_info(KER, IPLS_SHAPE_MID, kMidBS, RM, mid_seqf<BE_IN, START>(), partial ? 3 : kBigMap, grid.x,
-                       BE_IN, BE_OUT, START);
-  } else {
-    const int64_t tile = (int64_t)kBlock * 2 * kSmallR;
-    const int64_t tpp = (maxL + tile - 1) / tile;
-    const dim3 grid((unsigned)grid_blocks(kSmallMap, tpp * n_parts));
-    if constexpr (FIN)
-      hipLaunchKernelGGL((k_round<BE_IN, START, kSmallG, kSmallR, kSmallMap, kBlock>), grid, dim3(kBlock), 0, st,
-                         bufs, parts, k, (int)tpp, n_parts, secure, cnts);
-    else
-      hipLaunchKernelGGL((k_reduce<BE_IN, BE_OUT, START, kSmallG, kSmallR, true, kSmallMap>), grid, dim3(kBlock), 0,
-                         st, bufs, parts, k, (int)tpp, n_parts);
-    return launch_info(KER, IPLS_SHAPE_SMALL, kBlock, kSmallR, 0, kSmallMap, grid.x, BE_IN, BE_OUT, START);
-  }
-}
-
-ipls_launch_info launch_reduce(bool be_in, bool be_out, int start, int64_t maxL, int n_parts, hipStream_t st,
-                               const unsigned long long* const* bufs, const PartDesc* parts, int k) {
-#define LV(BI, BO)                                                                                         \
-  do {                                                                                                     \
-    if (start == kZero) return launch_reduce_v<BI, BO, kZero>(maxL, n_parts, st, bufs, parts, k);          \
-    else if (start == kFirst) return launch_reduce_v<BI, BO, kFirst>(maxL, n_parts, st, bufs, parts, k);   \
-    else return launch_reduce_v<BI, BO, kAccum>(maxL, n_parts, st, bufs, parts, k);                        \
-  } while (0)
-  if (be_in) { if (be_out) LV(true, true); else LV(true, false); }
-  else { if (be_out) LV(false, true); else LV(false, false); }
-#undef LV
-}
-
-// fused round: native-double Weights out, ZERO or ACCUM start (AGG is never
-// FIRST-started).  A one-block pre-pass folds each partition's count slot
-// (k + 2 scalar loads per partition) so that the wide kernel reads one value
-// per block instead of a k-long chain of dependent loads.
-ipls_launch_info launch_reduce_fin(bool be_in, int start, int secure, int64_t maxL, int n_parts, hipStream_t st,
-                                   const unsigned long long* const* bufs, const PartDesc* parts, int k,
-                                   double* cnts) {
-#define FIN(BI, ST)                                                                                   \
-  do {                                                                                                \
-    hipLaunchKernelGGL((k_round_counts<BI, ST>), dim3(n_parts), dim3(64), 0, st,                     \
-                       bufs, parts, k, n_parts, cnts);                                                 \
-    return launch_reduce_v<BI, false, ST, true>(maxL, n_parts, st, bufs, parts, k, secure, cnts);    \
-  } while (0)
-  if (be_in) { if (start == kZero) FIN(true, kZero); else FIN(true, kAccum); }
-  else { if (start == kZero) FIN(false, kZero); else FIN(false, kAccum); }
-#undef FIN
-}
-
-void launch_reduce_scalar(bool be_in, bool be_out, int start, dim3 grid, hipStream_t st,
-                          const unsigned long long* const* bufs, const PartDesc* parts, int k, int tpp,
-                          int64_t tile) {
-#define RS(BI, BO, ST) hipLaunchKernelGGL((k_reduce_scalar<BI, BO, ST>), grid, dim3(kBlock), 0, st, bufs, parts, k, tpp, tile)
-#define RS2(BI, BO) do { if (start == kZero) RS(BI, BO, kZero); else if (start == kFirst) RS(BI, BO, kFirst); else RS(BI, BO, kAccum); } while (0)
-  if (be_in) { if (be_out) RS2(true, true); else RS2(true, false); }
-  else { if (be_out) RS2(false, true); else RS2(false, false); }
-#undef RS2
-#undef RS
-}
-
 // Calls f with a value of the kernels' format type for a trainer format.
-template <class F>
-auto with_narrow(Fmt fmt, F&& f) {
+template <class F> auto with_narrow(Fmt fmt, F&& f) {
   switch (fmt) {
     case kFmtF32: return f(FmtF32{});
     case kFmtF16: return f(FmtF16{});
@@ -847,75 +589,126 @@ auto with_narrow(Fmt fmt, F&& f) {
   abort();
 }
 
-// ---- kernel dispatch: k_reduce_narrow (DEV_F32 / DEV_F16 / DEV_BF16 buckets) ----
-// One shape per element size (narrow_shape), for every grid; the two blocks
-// below say why floats and 16-bit elements differ in vectors per lane.
-// Floats: 1024-lane workgroups, 2 vectors of 4 floats per
-// lane (32 KiB of a bucket per block, 16 accumulator VGPRs), the next peer's 2
-// loads issued before this peer's values are added (PF = 1; 70 VGPRs, no
-// spills).  Same process, same buckets, single launches
-// (tools/reduce_f32_sweep.hip, profiles/f32_boundary/sweep_*.txt): config C's
-// 16 x 4M x 32 at 79.8 % of 8 TB/s against 70.3-77.0 % for the other
-// prefetching shapes of 256..1024 lanes x 2..8 vectors and 70.6-79.8 % without
-// the prefetch; 1 x 4M x 32 at 82.4 %, the best of the sweep; ETHModel's
-// 3 x 147,870 x 3 within 5 % of the best.
-// 16-bit formats: layout A of the sweep -- 8-B loads, 4 elements per lane per
-// vector, the same lane ^ 4 swap before the stores as for floats -- on
-// 1024-lane workgroups with 4 vectors per lane (32 KiB of a bucket per
-// block, 32 accumulator VGPRs), the next peer's 4 loads issued before this
-// peer's values are added (68-90 VGPRs over the start modes, no scratch).
-// Same process, same buckets, single launches, sums 128-B aligned as in the
-// arena (tools/reduce_h16_sweep.hip, profiles/h16_boundary/sweep_*.txt).  At
-// config C's 16 x 4M x 32 three shapes are level: this one 0.781-0.796 ms
-// (75.9-77.4 % of 8 TB/s), layout A's 512 x 2 0.791-0.792 ms, and layout B
-// (16-B loads, 8 elements per lane, pairs transposed across 8 lanes) at
-// 512 x 2 without the prefetch 0.771-0.799 ms, the fastest row for halves.
-// 1 x 4M x 32 decides: this shape 77.2 % (level with the column's best, B's
-// 1024 x 2 with the prefetch, 77.4 %, which has 73.3-73.7 % at config C)
-// against 69.2 % for B's 512 x 2 and 64.5 % for A's 512 x 2.  ETHModel's
-// 3 x 147,870 x 3 takes 7.5 us against 6.6 us for the tiles of 8,192 elements
-// and below (30 blocks instead of 57 or more).  Both layouts write 1.0000x the algorithmic bytes; without
-// the exchange A writes 1.114x and B 1.56-1.59x (pmc_sweep_WRITE_SIZE.csv).
-// Partial last tiles are scheduled first (map 3) as for k_reduce.  vec: every
-// bucket and destination is 16-B aligned; otherwise the same grid runs element
-// by element.
-struct NarrowShape {
-  int bs, r, pf, e;   // lanes, vectors per lane, next-peer prefetch, elements per lane per vector
-  int kernel;         // what the launch record names
-};
-template <class S>
-constexpr NarrowShape narrow_shape() {
-  return sizeof(typename S::elem) == 4 ? NarrowShape{1024, 2, 1, 4, IPLS_KERNEL_REDUCE_F32}
-                                       : NarrowShape{1024, 4, 1, 4, IPLS_KERNEL_REDUCE_H16};
+// The plan header is host-only: it takes the C-ABI's start modes, which are the
+// kernels' template starts, and states the map-2 grid and the default block again.
+static_assert(kZero == IPLS_START_ZERO && kFirst == IPLS_START_FIRST && kAccum == IPLS_START_ACCUM, "one start code");
+static_assert(kSmallBS == kBlock && kScalarBS == kBlock, "one default block");
+static_assert(plan_grid(2, 1) == grid_blocks(2, 1) && plan_grid(2, 8) == grid_blocks(2, 8) &&
+              plan_grid(2, 4097) == grid_blocks(2, 4097) && plan_grid(3, 4097) == grid_blocks(3, 4097), "one grid");
+
+// What a fold launch ran (ipls_agg_last_launch): tests assert that a case
+// reaches the kernel shape it was written for.
+ipls_launch_info launch_info(int kernel, int shape, int block, int r, int seqf, int map, int64_t grid, bool be_in,
+                             bool be_out, int start) {
+  return ipls_launch_info{kernel, shape, block, r, seqf, map, grid, be_in, be_out, start, 0};
 }
+ipls_launch_info launch_info(const ReducePlan& p, bool be_in, bool be_out, int start) {
+  return launch_info(p.kernel, p.shape, p.block, p.r, p.seqf, p.map, p.grid, be_in, be_out, start);
+}
+
+// ---- kernel dispatch: k_reduce / k_round, from plan_reduce (reduce_plan.hpp) ----
+// the template arguments of one wide fold, named as k_reduce and k_round name them
+template <int G_, int R_, int MAP_, int BS_, int SEQF_>
+struct Tiles {
+  static constexpr int G = G_, R = R_, MAP = MAP_, BS = BS_, SEQF = SEQF_;
+};
+template <bool BE_IN, bool BE_OUT, int START, bool FIN = false>
+ipls_launch_info launch_reduce_v(int64_t maxL, int n_parts, hipStream_t st, const unsigned long long* const* bufs,
+                                 const PartDesc* parts, int k, int secure = 0, const double* cnts = nullptr) {
+  constexpr int R = big_r(BE_IN, START), SEQF = big_seqf(BE_IN, START);
+  constexpr int RM = mid_r(BE_IN, START), SEQFM = mid_seqf(BE_IN, START);
+  const ReducePlan p = plan_reduce(BE_IN, START, FIN, maxL, n_parts);
+  const dim3 grid((unsigned)p.grid);
+  auto run = [&](auto t) {
+    typedef decltype(t) T;
+    if constexpr (FIN)
+      hipLaunchKernelGGL((k_round<BE_IN, START, T::G, T::R, T::MAP, T::BS, T::SEQF>), grid, dim3(T::BS), 0, st, bufs,
+                         parts, k, (int)p.tpp, n_parts, secure, cnts);
+    else
+      hipLaunchKernelGGL((k_reduce<BE_IN, BE_OUT, START, T::G, T::R, true, T::MAP, T::BS, T::SEQF>), grid,
+                         dim3(T::BS), 0, st, bufs, parts, k, (int)p.tpp, n_parts);
+  };
+  // exactly the (shape, map) pairs plan_reduce gives
+  switch (p.shape) {
+    case IPLS_SHAPE_HALF:
+      if constexpr (half_allowed(START, FIN)) {
+        if (p.map == 3) run(Tiles<kBigG, kHalfR, 3, kHalfBS, 0>{});
+        else run(Tiles<kBigG, kHalfR, kBigMap, kHalfBS, 0>{});
+      }
+      break;
+    case IPLS_SHAPE_BIG:
+      if (p.map == 3) run(Tiles<kBigG, R, 3, kBigBS, SEQF>{});
+      else if (p.map == 2) run(Tiles<kBigG, R, 2, kBigBS, SEQF>{});
+      else run(Tiles<kBigG, R, kBigMap, kBigBS, SEQF>{});
+      break;
+    case IPLS_SHAPE_MID:
+      if (p.map == 3) run(Tiles<kBigG, RM, 3, kMidBS, SEQFM>{});
+      else run(Tiles<kBigG, RM, kBigMap, kMidBS, SEQFM>{});
+      break;
+    default: run(Tiles<kSmallG, kSmallR, kSmallMap, kSmallBS, 0>{});
+  }
+  return launch_info(p, BE_IN, BE_OUT, START);
+}
+
+ipls_launch_info launch_reduce(bool be_in, bool be_out, int start, int64_t maxL, int n_parts, hipStream_t st,
+                               const unsigned long long* const* bufs, const PartDesc* parts, int k) {
+  return with_fold(be_in, be_out, start, [&](auto i, auto o, auto s) {
+    return launch_reduce_v<decltype(i)::value, decltype(o)::value, decltype(s)::value>(maxL, n_parts, st, bufs, parts, k);
+  });
+}
+
+// fused round: native-double Weights out, ZERO or ACCUM start (AGG is never
+// FIRST-started).  A one-block pre-pass folds each partition's count slot
+// (k + 2 scalar loads per partition) so that the wide kernel reads one value
+// per block instead of a k-long chain of dependent loads.
+ipls_launch_info launch_reduce_fin(bool be_in, int start, int secure, int64_t maxL, int n_parts, hipStream_t st,
+                                   const unsigned long long* const* bufs, const PartDesc* parts, int k,
+                                   double* cnts) {
+  return with_bool(be_in, [&](auto bi) {
+    return with_start_za(start, [&](auto s) {
+      constexpr bool BI = decltype(bi)::value;
+      constexpr int ST = decltype(s)::value;
+      hipLaunchKernelGGL((k_round_counts<BI, ST>), dim3(n_parts), dim3(64), 0, st, bufs, parts, k, n_parts, cnts);
+      return launch_reduce_v<BI, false, ST, true>(maxL, n_parts, st, bufs, parts, k, secure, cnts);
+    });
+  });
+}
+
+// k_reduce_scalar on plan_reduce_scalar's grid
+void launch_reduce_scalar(bool be_in, bool be_out, int start, const ReducePlan& p, hipStream_t st,
+                          const unsigned long long* const* bufs, const PartDesc* parts, int k) {
+  with_fold(be_in, be_out, start, [&](auto bi, auto bo, auto s) {
+    hipLaunchKernelGGL((k_reduce_scalar<decltype(bi)::value, decltype(bo)::value, decltype(s)::value>),
+                       dim3((unsigned)p.grid), dim3(kBlock), 0, st, bufs, parts, k, (int)p.tpp, p.tile);
+  });
+}
+
+// ---- kernel dispatch: k_reduce_narrow, from plan_reduce_narrow (reduce_plan.hpp) ----
+// Element by element (!vec) the kernel has no map 3 and no prefetch.
 template <class S>
 ipls_launch_info launch_reduce_narrow(bool be_out, int start, bool vec, int64_t maxL, int n_parts, hipStream_t st,
                                       const typename S::elem* const* bufs, const PartDesc* parts, int k) {
-  constexpr NarrowShape K = narrow_shape<S>();
-  const int64_t tile = (int64_t)K.bs * K.e * K.r;
-  const int64_t tpp = (maxL + tile - 1) / tile;
-  const bool partial = tpp > 1 && maxL % tile != 0;
-  const dim3 grid((unsigned)(tpp * n_parts));
-#define RN(BO, ST, MAP, V)                                                                                       \
-  hipLaunchKernelGGL((k_reduce_narrow<S, BO, ST, K.r, K.bs, MAP, V, (V ? K.pf : 0), K.e>), grid, dim3(K.bs), 0, st, \
-                     bufs, parts, k, (int)tpp, n_parts)
-#define RN3(BO, ST)                                         \
-  do {                                                      \
-    if (!vec) RN(BO, ST, 0, false);                         \
-    else if (partial) RN(BO, ST, 3, true);                  \
-    else RN(BO, ST, 0, true);                               \
-  } while (0)
-#define RN2(BO) do { if (start == kZero) RN3(BO, kZero); else if (start == kFirst) RN3(BO, kFirst); else RN3(BO, kAccum); } while (0)
-  if (be_out) RN2(true);
-  else RN2(false);
-#undef RN2
-#undef RN3
-#undef RN
-  return launch_info(K.kernel, 0, K.bs, K.r, vec ? 1 : 0, (vec && partial) ? 3 : 0, grid.x, false, be_out, start);
+  constexpr NarrowShape K = narrow_shape(sizeof(typename S::elem));
+  const ReducePlan p = plan_reduce_narrow(sizeof(typename S::elem), false, vec, maxL, n_parts);
+  const dim3 grid((unsigned)p.grid);
+  with_bool(be_out, [&](auto bo) {
+    with_start(start, [&](auto s) {
+      auto run = [&](auto map, auto v) {
+        constexpr bool V = decltype(v)::value;
+        hipLaunchKernelGGL((k_reduce_narrow<S, decltype(bo)::value, decltype(s)::value, K.r, K.bs, decltype(map)::value,
+                                            V, (V ? K.pf : 0), K.e>),
+                           grid, dim3(K.bs), 0, st, bufs, parts, k, (int)p.tpp, n_parts);
+      };
+      if (!vec) run(Int<0>{}, std::false_type{});
+      else if (p.map == 3) run(Int<3>{}, std::true_type{});
+      else run(Int<0>{}, std::true_type{});
+    });
+  });
+  return launch_info(p, false, be_out, start);
 }
 
 // ---- kernel dispatch: k_round_narrow (the fused round over DEV_F32 / DEV_F16 / DEV_BF16 buckets) ----
-// The fold's shape (narrow_shape<S>: 1024 lanes x 2 vectors of floats, x 4 of
+// The fold's shape (narrow_shape: 1024 lanes x 2 vectors of floats, x 4 of
 // 16-bit elements, the next peer prefetched), every operand 16-B aligned; the
 // count pre-pass first, as for k_round.  A: the averages' format (S when the
 // round writes none).  ZERO or ACCUM start; partial last tiles first (map 3).
@@ -923,24 +716,15 @@ template <class S, class A>
 ipls_launch_info launch_round_narrow(int start, int secure, int64_t maxL, int n_parts, hipStream_t st,
                                      const typename S::elem* const* bufs, const PartDesc* parts, int k,
                                      double* cnts) {
-  constexpr NarrowShape K = narrow_shape<S>();
-  const int64_t tile = (int64_t)K.bs * K.e * K.r;
-  const int64_t tpp = (maxL + tile - 1) / tile;
-  const bool partial = tpp > 1 && maxL % tile != 0;
-  const int map = partial ? 3 : 0;
-  const dim3 grid((unsigned)(tpp * n_parts));
-#define RNF(ST)                                                                                              \
-  do {                                                                                                       \
-    hipLaunchKernelGGL((k_round_counts_narrow<S, ST>), dim3(n_parts), dim3(64), 0, st, bufs, parts, k,       \
-                       n_parts, cnts);                                                                       \
-    hipLaunchKernelGGL((k_round_narrow<S, A, ST, K.r, K.bs, K.pf>), grid, dim3(K.bs), 0, st, bufs, parts, k, \
-                       (int)tpp, n_parts, map, secure, (const double*)cnts);                                 \
-  } while (0)
-  if (start == kZero) RNF(kZero);
-  else RNF(kAccum);
-#undef RNF
-  return launch_info(sizeof(typename S::elem) == 4 ? IPLS_KERNEL_ROUND_F32 : IPLS_KERNEL_ROUND_H16, 0, K.bs, K.r, 1,
-                     map, grid.x, false, false, start);
+  constexpr NarrowShape K = narrow_shape(sizeof(typename S::elem));
+  const ReducePlan p = plan_reduce_narrow(sizeof(typename S::elem), true, true, maxL, n_parts);
+  with_start_za(start, [&](auto s) {
+    constexpr int ST = decltype(s)::value;
+    hipLaunchKernelGGL((k_round_counts_narrow<S, ST>), dim3(n_parts), dim3(64), 0, st, bufs, parts, k, n_parts, cnts);
+    hipLaunchKernelGGL((k_round_narrow<S, A, ST, K.r, K.bs, K.pf>), dim3((unsigned)p.grid), dim3(K.bs), 0, st, bufs,
+                       parts, k, (int)p.tpp, n_parts, p.map, secure, (const double*)cnts);
+  });
+  return launch_info(p, false, false, start);
 }
 
 // Core of accumulate / reduce_batch: all pointers device-resident.  The
@@ -1018,14 +802,12 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
       const auto* s0 = (const unsigned long long*)bufs[0];
       const unsigned blocks =
           std::max(1u, std::min<unsigned>(blocks_for((L >> 1), kBlock * 4), host_src ? 128u : 4096u));
-#define F1(BI, BO, ST) hipLaunchKernelGGL((k_fold1<BI, BO, ST>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, L)
-#define F1S(BI, BO) do { if (start == kZero) F1(BI, BO, kZero); else if (start == kFirst) F1(BI, BO, kFirst); else F1(BI, BO, kAccum); } while (0)
-      if (be_in) { if (be_out) F1S(true, true); else F1S(true, false); }
-      else { if (be_out) F1S(false, true); else F1S(false, false); }
-#undef F1S
-#undef F1
+      with_fold(be_in, be_out, start, [&](auto bi, auto bo, auto s) {
+        hipLaunchKernelGGL((k_fold1<decltype(bi)::value, decltype(bo)::value, decltype(s)::value>), dim3(blocks),
+                           dim3(kBlock), 0, h->stream, d0, s0, L);
+      });
       HIP_TRY(h, hipGetLastError());
-      h->last_launch = launch_info(IPLS_KERNEL_FOLD1, 0, kBlock, 4, 0, 0, blocks, be_in, be_out, kstart(start));
+      h->last_launch = launch_info(IPLS_KERNEL_FOLD1, 0, kBlock, 4, 0, 0, blocks, be_in, be_out, start);
       if (!ext_dst)
         if (uint8_t* f = zero_flag(h, p_first, target)) *f = 0;
       return IPLS_OK;
@@ -1042,14 +824,14 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
       with_narrow(fmt_in, [&](auto s) {
         typedef decltype(s) S;
         const auto* s0 = (const typename S::elem*)bufs[0];
-        if (start == IPLS_START_ZERO)
-          hipLaunchKernelGGL((k_fold1_narrow<S, kZero, kFold1NarrowR>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, L);
-        else
-          hipLaunchKernelGGL((k_fold1_narrow<S, kAccum, kFold1NarrowR>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, L);
+        with_start_za(start, [&](auto st) {   // never FIRST (the guard above), never BE out
+          hipLaunchKernelGGL((k_fold1_narrow<S, decltype(st)::value, kFold1NarrowR>), dim3(blocks), dim3(kBlock), 0,
+                             h->stream, d0, s0, L);
+        });
       });
       HIP_TRY(h, hipGetLastError());
       h->last_launch = launch_info(fmt_size(fmt_in) == 4 ? IPLS_KERNEL_FOLD1_F32 : IPLS_KERNEL_FOLD1_H16, 0, kBlock,
-                                   kFold1NarrowR, 1, 0, blocks, false, false, kstart(start));
+                                   kFold1NarrowR, 1, 0, blocks, false, false, start);
       if (!ext_dst)
         if (uint8_t* f = zero_flag(h, p_first, target)) *f = 0;
       return IPLS_OK;
@@ -1101,7 +883,7 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
       h->last_launch = with_narrow(fmt_in, [&](auto s) {
         typedef decltype(s) S;
         return with_narrow(fin->avg ? fin->fmt : fmt_in, [&](auto a) {
-          return launch_round_narrow<S, decltype(a)>(kstart(start), h->secure, maxL, n_parts, h->stream,
+          return launch_round_narrow<S, decltype(a)>(start, h->secure, maxL, n_parts, h->stream,
                                                      (const typename S::elem* const*)dbufs, dparts, k, h->d_cnt);
         });
       });
@@ -1115,18 +897,15 @@ int reduce_dev(ipls_dev* h, int p_first, int n_parts, const void* const* bufs, i
   if (tr_in) {
     h->last_launch = with_narrow(fmt_in, [&](auto s) {
       typedef decltype(s) S;
-      return launch_reduce_narrow<S>(be_out, kstart(start), aligned16, maxL, n_parts, h->stream,
+      return launch_reduce_narrow<S>(be_out, start, aligned16, maxL, n_parts, h->stream,
                                      (const typename S::elem* const*)dbufs, dparts, k);
     });
   } else if (aligned16) {
     h->last_launch = launch_reduce(be_in, be_out, start, maxL, n_parts, h->stream, dbufs, dparts, k);
   } else {
-    const int64_t tile = (int64_t)kBlock * 8;
-    const int tpp = (int)((maxL + tile - 1) / tile);
-    launch_reduce_scalar(be_in, be_out, start, dim3((unsigned)tpp * n_parts), h->stream, dbufs, dparts, k, tpp,
-                         tile);
-    h->last_launch = launch_info(IPLS_KERNEL_REDUCE_SCALAR, 0, kBlock, 1, 0, 0, (int64_t)tpp * n_parts, be_in, be_out,
-                                 kstart(start));
+    const ReducePlan p = plan_reduce_scalar(maxL, n_parts);
+    launch_reduce_scalar(be_in, be_out, start, p, h->stream, dbufs, dparts, k);
+    h->last_launch = launch_info(p, be_in, be_out, start);
   }
   HIP_TRY(h, hipGetLastError());
   if (!ext_dst)
@@ -1674,7 +1453,7 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
   if (be) hipLaunchKernelGGL((k_fold1<true, false, kAccum>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, n);
   else hipLaunchKernelGGL((k_fold1<false, false, kAccum>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, n);
   HIP_TRY(h, hipGetLastError());
-  h->last_launch = launch_info(IPLS_KERNEL_FOLD1, 0, kBlock, 4, 0, 0, blocks, be, false, kstart(IPLS_START_ACCUM));
+  h->last_launch = launch_info(IPLS_KERNEL_FOLD1, 0, kBlock, 4, 0, 0, blocks, be, false, IPLS_START_ACCUM);
   *ticket = h->ticket_next++;
   return end_batch(h);
 }
@@ -2269,7 +2048,8 @@ static int finalize_range(ipls_dev* h, int p0, int np) {
 
 // GetPartitions' divide (IPLS.java:1159-1174) of Weights[p0..p0+np) into d_out,
 // partition p at flat_off[p] - flat_off[p0].
-static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, bool be) {
+// The divide's descriptor table for Weights[p0..p0+np), uploaded, and its tiles per partition (0: none).
+static int divide_table(ipls_dev* h, int p0, int np, const DivDesc** dtab, int* tpp) {
   std::vector<DivDesc> dd(np);
   int64_t maxn = 0;
   for (int q = 0; q < np; ++q) {
@@ -2277,16 +2057,25 @@ static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, 
     dd[q] = DivDesc{h->len[p], h->w_off[p], h->flat_off[p] - h->flat_off[p0]};
     maxn = std::max(maxn, h->len[p] - 1);
   }
-  if (maxn <= 0) return IPLS_OK;
-  void* dtab = nullptr;
-  if (int rc = upload_table(h, dd.data(), dd.size() * sizeof(DivDesc), &dtab)) return rc;
-  const int64_t tile = kDivTile;
-  const int tpp = (int)((maxn + tile - 1) / tile);
-  const dim3 g((unsigned)tpp * np);
-#define DIV(B, S) hipLaunchKernelGGL((k_divide<B, S>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab, (const double*)h->arena, d_out, tpp)
-  if (be) { if (h->secure) DIV(true, true); else DIV(true, false); }
-  else { if (h->secure) DIV(false, true); else DIV(false, false); }
-#undef DIV
+  *tpp = (int)((std::max<int64_t>(maxn, 0) + kDivTile - 1) / kDivTile);
+  if (*tpp == 0) return IPLS_OK;
+  void* d = nullptr;
+  if (int rc = upload_table(h, dd.data(), dd.size() * sizeof(DivDesc), &d)) return rc;
+  *dtab = (const DivDesc*)d;
+  return IPLS_OK;
+}
+
+static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, bool be) {
+  const DivDesc* dtab = nullptr;
+  int tpp = 0;
+  if (int rc = divide_table(h, p0, np, &dtab, &tpp)) return rc;
+  if (tpp == 0) return IPLS_OK;
+  with_bool(be, [&](auto b) {
+    with_bool(h->secure != 0, [&](auto sec) {
+      hipLaunchKernelGGL((k_divide<decltype(b)::value, decltype(sec)::value>), dim3((unsigned)tpp * np), dim3(kBlock),
+                         0, h->stream, dtab, (const double*)h->arena, d_out, tpp);
+    });
+  });
   HIP_TRY(h, hipGetLastError());
   return IPLS_OK;
 }
@@ -2294,26 +2083,16 @@ static int divide_range(ipls_dev* h, int p0, int np, unsigned long long* d_out, 
 // The same divide narrowed to a trainer format (k_divide_narrow): d_out holds
 // floats, halves or bfloat16s.
 static int divide_range_narrow(ipls_dev* h, int p0, int np, void* d_out, Fmt fmt) {
-  std::vector<DivDesc> dd(np);
-  int64_t maxn = 0;
-  for (int q = 0; q < np; ++q) {
-    const int p = p0 + q;
-    dd[q] = DivDesc{h->len[p], h->w_off[p], h->flat_off[p] - h->flat_off[p0]};
-    maxn = std::max(maxn, h->len[p] - 1);
-  }
-  if (maxn <= 0) return IPLS_OK;
-  void* dtab = nullptr;
-  if (int rc = upload_table(h, dd.data(), dd.size() * sizeof(DivDesc), &dtab)) return rc;
-  const int tpp = (int)((maxn + kDivTile - 1) / kDivTile);
-  const dim3 g((unsigned)tpp * np);
+  const DivDesc* dtab = nullptr;
+  int tpp = 0;
+  if (int rc = divide_table(h, p0, np, &dtab, &tpp)) return rc;
+  if (tpp == 0) return IPLS_OK;
   with_narrow(fmt, [&](auto s) {
     typedef decltype(s) S;
-#define DIVN(SEC)                                                                                          \
-  hipLaunchKernelGGL((k_divide_narrow<S, SEC>), g, dim3(kBlock), 0, h->stream, (const DivDesc*)dtab,      \
-                     (const double*)h->arena, (typename S::elem*)d_out, tpp)
-    if (h->secure) DIVN(true);
-    else DIVN(false);
-#undef DIVN
+    with_bool(h->secure != 0, [&](auto sec) {
+      hipLaunchKernelGGL((k_divide_narrow<S, decltype(sec)::value>), dim3((unsigned)tpp * np), dim3(kBlock), 0,
+                         h->stream, dtab, (const double*)h->arena, (typename S::elem*)d_out, tpp);
+    });
   });
   HIP_TRY(h, hipGetLastError());
   return IPLS_OK;
@@ -2551,14 +2330,14 @@ int dev_other_replica(ipls_dev* h, int p, int32_t aggregator, const void* src, i
   if (n > 0) {
     const bool vec = al16(dst) && al16(d);
     const dim3 g = ew_grid(n, vec, 4096);
-#define FN(B, F)                                                                                         \
-  do {                                                                                                   \
-    if (vec) hipLaunchKernelGGL((k_fold_n<B, F, true>), g, dim3(kBlock), 0, h->stream, dst, d, n);      \
-    else hipLaunchKernelGGL((k_fold_n<B, F, false>), g, dim3(kBlock), 0, h->stream, dst, d, n);         \
-  } while (0)
-    if (be) { if (first) FN(true, true); else FN(true, false); }
-    else { if (first) FN(false, true); else FN(false, false); }
-#undef FN
+    with_bool(be, [&](auto b) {
+      with_bool(first, [&](auto f) {
+        with_bool(vec, [&](auto v) {
+          hipLaunchKernelGGL((k_fold_n<decltype(b)::value, decltype(f)::value, decltype(v)::value>), g, dim3(kBlock),
+                             0, h->stream, dst, d, n);
+        });
+      });
+    });
     e = hipGetLastError();
   }
   if (e == hipSuccess && (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE)) e = hipStreamSynchronize(h->stream);
@@ -2746,26 +2525,24 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
     out = (unsigned long long*)h->d_scratch;
   const bool vec = al16(d) && al16(out);
   const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
-#define SPL(BI, BO)                                                                                              \
-  do {                                                                                                           \
-    if (vec) hipLaunchKernelGGL((k_split<BI, BO, 0, true>), g, dim3(kBlock), 0, h->stream, d, (int64_t)0, ncopy, L, out); \
-    else hipLaunchKernelGGL((k_split<BI, BO, 0, false>), g, dim3(kBlock), 0, h->stream, d, (int64_t)0, ncopy, L, out); \
-  } while (0)
-#define SPLN(BO)                                                                                                 \
-  do {                                                                                                           \
-    if (vec) hipLaunchKernelGGL((k_split_narrow<S, BO, 0, true>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, (int64_t)0, ncopy, L, out); \
-    else hipLaunchKernelGGL((k_split_narrow<S, BO, 0, false>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, (int64_t)0, ncopy, L, out); \
-  } while (0)
+  auto flags = [&](auto&& f) {   // f(be_out, vec)
+    with_bool(be_out, [&](auto bo) { with_bool(vec, [&](auto v) { f(bo, v); }); });
+  };
   if (fmt_trainer(fmt))
     with_narrow(fmt, [&](auto s) {
       typedef decltype(s) S;
-      if (be_out) SPLN(true);
-      else SPLN(false);
+      flags([&](auto bo, auto v) {
+        hipLaunchKernelGGL((k_split_narrow<S, decltype(bo)::value, 0, decltype(v)::value>), g, dim3(kBlock), 0,
+                           h->stream, (const typename S::elem*)d, (int64_t)0, ncopy, L, out);
+      });
     });
-  else if (be_in) { if (be_out) SPL(true, true); else SPL(true, false); }
-  else { if (be_out) SPL(false, true); else SPL(false, false); }
-#undef SPLN
-#undef SPL
+  else
+    with_bool(be_in, [&](auto bi) {
+      flags([&](auto bo, auto v) {
+        hipLaunchKernelGGL((k_split<decltype(bi)::value, decltype(bo)::value, 0, decltype(v)::value>), g, dim3(kBlock),
+                           0, h->stream, d, (int64_t)0, ncopy, L, out);
+      });
+    });
   HIP_TRY(h, hipGetLastError());
   if (host_out) return d2h(h, dst, out, (size_t)L * 8);
   return IPLS_OK;
@@ -2792,9 +2569,11 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
   const int64_t seg = std::max<int64_t>(0, std::min(n, h->flat_total) - h->flat_base);
   const Fmt fmt = kind_trainer(src_kind) ? kind_fmt(src_kind) : kFmtF64;
   const int64_t esz = fmt_size(fmt);
-  if (kind_trainer_host(src_kind)) {
-    // as below, 4 or 2 B per element: only the owned partitions' values cross PCIe
-    if ((uintptr_t)flat & (uintptr_t)(esz - 1))
+  if (kind_trainer_host(src_kind) || src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
+    // from host memory only the owned partitions' values cross PCIe, at 8, 4
+    // or 2 B per element: the others are split by OrganizeGradients too, but
+    // never accumulated (IPLS.java:1737-1743), so their bytes are never read here
+    if (fmt_trainer(fmt) && ((uintptr_t)flat & (uintptr_t)(esz - 1)))
       return fail(h, IPLS_E_INVAL, "host vector not %d-byte aligned", (int)esz);
     if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(seg, 1) * esz)) return rc;
     const char* base = (const char*)flat + esz * h->flat_base;
@@ -2802,19 +2581,6 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
       const int64_t lo = h->flat_off[owned[i]] - h->flat_base;
       if (nc[owned[i]] > 0)
         if (int rc = stage_h2d(h, (char*)h->d_scratch + esz * lo, base + esz * lo, (size_t)nc[owned[i]] * esz)) return rc;
-    }
-    d = (const unsigned long long*)h->d_scratch;
-    be = false;
-  } else if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
-    // from host memory only the owned partitions' values cross PCIe: the
-    // others are split by OrganizeGradients too, but never accumulated
-    // (IPLS.java:1737-1743), so their bytes are never read here
-    if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(seg, 1) * 8)) return rc;
-    const char* base = (const char*)flat + 8 * h->flat_base;
-    for (int i = 0; i < n_owned; ++i) {
-      const int64_t lo = h->flat_off[owned[i]] - h->flat_base;
-      if (nc[owned[i]] > 0)
-        if (int rc = stage_h2d(h, (char*)h->d_scratch + 8 * lo, base + 8 * lo, (size_t)nc[owned[i]] * 8)) return rc;
     }
     d = (const unsigned long long*)h->d_scratch;
     be = src_kind == IPLS_HOST_BE;
@@ -2835,26 +2601,24 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
     // Logically-zero accumulator: MODE 2 writes +0.0 + v without reading it
     // (the bits of a fold into zeros)
-#define UPD(BI, M)                                                                                              \
-  do {                                                                                                          \
-    if (vec) hipLaunchKernelGGL((k_split<BI, false, M, true>), g, dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc); \
-    else hipLaunchKernelGGL((k_split<BI, false, M, false>), g, dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc); \
-  } while (0)
-#define UPDN(M)                                                                                                 \
-  do {                                                                                                          \
-    if (vec) hipLaunchKernelGGL((k_split_narrow<S, false, M, true>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, lo, nc[p], L, acc); \
-    else hipLaunchKernelGGL((k_split_narrow<S, false, M, false>), g, dim3(kBlock), 0, h->stream, (const typename S::elem*)d, lo, nc[p], L, acc); \
-  } while (0)
+    auto flags = [&](auto&& f) {   // f(zero, vec)
+      with_bool(zero, [&](auto z) { with_bool(vec, [&](auto v) { f(z, v); }); });
+    };
     if (fmt_trainer(fmt))
       with_narrow(fmt, [&](auto s) {
         typedef decltype(s) S;
-        if (zero) UPDN(2);
-        else UPDN(1);
+        flags([&](auto z, auto v) {
+          hipLaunchKernelGGL((k_split_narrow<S, false, decltype(z)::value ? 2 : 1, decltype(v)::value>), g,
+                             dim3(kBlock), 0, h->stream, (const typename S::elem*)d, lo, nc[p], L, acc);
+        });
       });
-    else if (be) { if (zero) UPD(true, 2); else UPD(true, 1); }
-    else { if (zero) UPD(false, 2); else UPD(false, 1); }
-#undef UPDN
-#undef UPD
+    else
+      with_bool(be, [&](auto bi) {
+        flags([&](auto z, auto v) {
+          hipLaunchKernelGGL((k_split<decltype(bi)::value, false, decltype(z)::value ? 2 : 1, decltype(v)::value>), g,
+                             dim3(kBlock), 0, h->stream, d, lo, nc[p], L, acc);
+        });
+      });
     HIP_TRY(h, hipGetLastError());
     h->agg_zero[p] = 0;
   }
@@ -3351,16 +3115,14 @@ int ipls_encode_secure(const void* src, void* dst, int64_t n, int src_kind, int 
   const bool bi = src_kind == IPLS_DEV_BE, bo = dst_kind == IPLS_DEV_BE;
   const bool vec = al16(s) && al16(d);
   const dim3 g = ew_grid(n, vec, 8192);
-#define ENC(BI, BO)                                                                                     \
-  do {                                                                                                  \
-    if (vec) hipLaunchKernelGGL((k_encode_secure<BI, BO, true>), g, dim3(kBlock), 0, st, s, d, n);      \
-    else hipLaunchKernelGGL((k_encode_secure<BI, BO, false>), g, dim3(kBlock), 0, st, s, d, n);         \
-  } while (0)
-  if (bi && bo) ENC(true, true);
-  else if (bi) ENC(true, false);
-  else if (bo) ENC(false, true);
-  else ENC(false, false);
-#undef ENC
+  with_bool(bi, [&](auto i) {
+    with_bool(bo, [&](auto o) {
+      with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((k_encode_secure<decltype(i)::value, decltype(o)::value, decltype(v)::value>), g,
+                           dim3(kBlock), 0, st, s, d, n);
+      });
+    });
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(nullptr, IPLS_E_DEVICE, "k_encode_secure: %s", hipGetErrorString(e));
   return IPLS_OK;

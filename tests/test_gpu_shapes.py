@@ -1,7 +1,7 @@
 """GPU parity of the launch shapes the production sizes take.
 
 The fold kernel's dispatch picks a tile shape by how many tiles a batch fills
-(engine.hip launch_reduce_v: big = 1024 lanes x 16 vectors, half = 512 lanes
+(reduce_plan.hpp plan_reduce: big = 1024 lanes x 16 vectors, half = 512 lanes
 x 16 vectors (fewer than 1024 whole big tiles, ZERO/FIRST start), mid = 256
 lanes x 16 vectors (8 for big-endian input), small = 256 lanes x 8 peers in
 flight).

@@ -1,7 +1,7 @@
 """Seams and special values of the wide fold shapes, at the smallest sizes that reach them.
 
 engine.hip launch_reduce_v runs reduce_tiles (ipls_kernels.hpp) in four
-shapes.  tests/test_gpu_shapes.py and four tests of tests/test_gpu_parity.py
+shapes, chosen by plan_reduce (reduce_plan.hpp).  tests/test_gpu_shapes.py and four tests of tests/test_gpu_parity.py
 reach the three wide ones (mid = 256 lanes, half = 512, big = 1024) at
 production sizes, with uniform buckets and mostly by checksum; the edge sweeps
 of the suite all run the small shape, in which the PAIRS epilogue of the fused
@@ -33,7 +33,7 @@ partition and by full reads of the first 2 * KMAX partitions (every rotation
 class at both parities of the averages), of the first of those with REP, and
 of the last two.  After a round AGG and REP read as +0.0.  A case that lands
 on another shape than written fails.  The last test checks that the records
-seen are exactly the combinations launch_reduce_v can emit for mid, half and
+seen are exactly the combinations plan_reduce can give for mid, half and
 big (expected_combinations()).
 
 What the geometry forbids, found while writing the cases:
@@ -94,7 +94,7 @@ def O():
 
 
 # ---------------------------------------------------------------------------
-# the combinations launch_reduce_v can emit for the wide shapes, in one place
+# the combinations plan_reduce can give for the wide shapes, in one place
 # ---------------------------------------------------------------------------
 def variant(ipls, shape, be_in, start):
     """(lanes, 16-B vectors per lane, SEQ code) of a wide shape: half is 512 x
@@ -620,7 +620,7 @@ def test_many_tiny_partitions(ipls, O, P, L):
 
 def test_every_combination_ran(ipls):
     """The launch records asserted above are exactly the combinations
-    launch_reduce_v can emit for the mid, half and big shapes (needs the
+    plan_reduce can give for the mid, half and big shapes (needs the
     whole file to have run)."""
     want = expected_combinations(ipls)
     assert SEEN == want, f"never launched: {sorted(want - SEEN)}; unexpected: {sorted(SEEN - want)}"

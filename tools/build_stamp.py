@@ -20,7 +20,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "ipls-java-api_amd" / "csrc"
-KERNEL_SOURCES = ("ipls_kernels.hpp", "engine.hip")
+KERNEL_SOURCES = ("ipls_kernels.hpp", "engine.hip", "reduce_plan.hpp")
 LIB_SOURCES = ("ipls-java-api_amd/csrc", "include/ipls_agg.h", "ipls-java-api_amd/Makefile")
 
 
