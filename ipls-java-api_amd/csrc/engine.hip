@@ -37,11 +37,13 @@
 #include "ipls_kernels.hpp"
 #include "javaser.hpp"
 #include "engine.hpp"
+#include "operand.hpp"
 #include "pubsub_host.hpp"
 #include "reduce_plan.hpp"
 
 using namespace ipls;
 using namespace ipls::reduceplan;
+namespace op = ipls::operand;
 
 namespace {
 
@@ -204,6 +206,10 @@ int fail(ipls_dev* h, int code, const char* fmt, ...) {
   g_tls_err = buf;
   return code;
 }
+
+// What a call returns when op::resolve did not say kTake: IPLS_OK for a no-op,
+// else the refusal's code with its text as the handle's error.
+int not_taken(ipls_dev* h, const op::Refusal& why) { return why.code ? fail(h, why.code, "%s", why.text) : IPLS_OK; }
 
 int flush_pending(ipls_dev* h);
 
@@ -554,16 +560,31 @@ static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static dim3 ew_grid(int64_t n, bool vec, unsigned cap) {
   return dim3(std::max(1u, vec ? blocks_for(n, kEwTile) : std::min<unsigned>(blocks_for(n, kBlock), cap)));
 }
-static void launch_bswap(hipStream_t st, const unsigned long long* in, unsigned long long* out, int64_t n) {
-  if (al16(in) && al16(out)) hipLaunchKernelGGL(k_bswap64<true>, ew_grid(n, true, 4096), dim3(kBlock), 0, st, in, out, n);
-  else hipLaunchKernelGGL(k_bswap64<false>, ew_grid(n, false, 4096), dim3(kBlock), 0, st, in, out, n);
-}
 
 // ---- runtime flags -> template arguments ----
 // Each helper calls f with a value whose type carries the flag as a constant
 // (decltype(x)::value; a format is the type itself), so a launch site names
 // the combinations it instantiates.  The lambdas only launch.
 template <class F> auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+static void launch_bswap(hipStream_t st, const unsigned long long* in, unsigned long long* out, int64_t n) {
+  with_bool(al16(in) && al16(out), [&](auto v) {
+    hipLaunchKernelGGL(k_bswap64<decltype(v)::value>, ew_grid(n, decltype(v)::value, 4096), dim3(kBlock), 0, st, in, out, n);
+  });
+}
+// Host bytes into the scratch buffer (grown to hold `cap` bytes if that is more) on the handle's stream.
+int to_scratch(ipls_dev* h, const void* src, size_t bytes, size_t cap = 0) {
+  if (int rc = ensure_scratch(h, std::max<size_t>({bytes, cap, 1}))) return rc;
+  return stage_h2d(h, h->d_scratch, src, bytes);
+}
+// Its mirror: the big-endian bytes of n device doubles, byte-swapped into the scratch buffer, then copied out.
+int be_to_host(ipls_dev* h, void* dst, const void* src, int64_t n) {
+  if (int rc = ensure_scratch(h, (size_t)n * 8)) return rc;
+  launch_bswap(h->stream, (const unsigned long long*)src, (unsigned long long*)h->d_scratch, n);
+  HIP_TRY(h, hipGetLastError());
+  return d2h(h, dst, h->d_scratch, (size_t)n * 8);
+}
+
 template <int V> using Int = std::integral_constant<int, V>;
 template <class F> auto with_start(int start, F&& f) {
   return start == kZero ? f(Int<kZero>{}) : start == kFirst ? f(Int<kFirst>{}) : f(Int<kAccum>{});
@@ -954,12 +975,6 @@ int partition_geometry(const ipls_agg_cfg* c, std::vector<int64_t>& len, std::ve
   return IPLS_OK;
 }
 
-int host_decode_count(int kind, int64_t n, int64_t L, ipls_dev* h) {
-  if (n < L) return fail(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n, (long long)L);
-  (void)kind;
-  return IPLS_OK;
-}
-
 }  // namespace
 
 // ===========================================================================
@@ -1259,124 +1274,50 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
   if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
-  if (!src) return IPLS_OK;  // Gradient == null: the Updater loops do nothing (Updater.java:115)
-  HIP_TRY(h, dev_use(h->device));
+  // a null source is Gradient == null: the Updater loops do nothing (Updater.java:115)
   const int64_t L = h->len[p];
-  const void* dptr = nullptr;
-  bool be = false, staged = false;
-  Fmt tr = kFmtF64;   // a trainer format (floats, halves, bfloat16s), else doubles by `be`
-  switch (src_kind) {
-    case IPLS_DEV_F64:
-    case IPLS_DEV_BE:
-      if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
-      dptr = src;
-      be = src_kind == IPLS_DEV_BE;
-      break;
-    case IPLS_HOST_F64:
-    case IPLS_HOST_BE: {
-      if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
-      be = src_kind == IPLS_HOST_BE;
-      void* alias = nullptr;
-      if (((uintptr_t)src & 7) == 0 && (size_t)L * 8 >= (1u << 16) && is_pinned_host(src, &alias) && alias) {
-        // Zero copy: the fold kernel reads the pinned bucket over PCIe (no
-        // staging copy, no second pass).  The call returns once the kernel
-        // is done with the caller's bytes.
-        const void* bl[1] = {alias};
-        if (int rc = reduce_dev(h, p, 1, bl, 1, be_fmt(be), IPLS_START_ACCUM, target, nullptr, false, nullptr, true))
-          return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return IPLS_OK;
-      }
-      if (int rc = stage_bucket(h, src, (size_t)L * 8, &dptr)) return rc;
-      staged = true;
-      break;
+  op::Resolved v;
+  if (op::resolve(op::kAccumulate, src, n, src_kind, L, &v) != op::kTake) return not_taken(h, v.why);
+  HIP_TRY(h, dev_use(h->device));
+  // a co-located trainer's float / half / bfloat16 bucket is widened in the fold (Model.java:423); from the
+  // host 4 or 2 B per element cross PCIe
+  const size_t bytes = (size_t)L * fmt_size(v.fmt);
+  const void* dptr = v.ptr;
+  if (v.host) {
+    void* alias = nullptr;
+    if (v.from == op::kRaw && !fmt_trainer(v.fmt) && op::zero_copy_arrival(v.ptr, bytes) && is_pinned_host(v.ptr, &alias) &&
+        alias) {
+      // Zero copy: the fold kernel reads the pinned bucket over PCIe (no
+      // staging copy, no second pass).  The call returns once the kernel
+      // is done with the caller's bytes.
+      const void* bl[1] = {alias};
+      if (int rc = reduce_dev(h, p, 1, bl, 1, v.fmt, IPLS_START_ACCUM, target, nullptr, false, nullptr, true)) return rc;
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      return IPLS_OK;
     }
-    case IPLS_DEV_F32:
-    case IPLS_DEV_F16:
-    case IPLS_DEV_BF16:
-      // a co-located trainer's float / half / bfloat16 bucket, widened in the fold (Model.java:423)
-      tr = kind_fmt(src_kind);
-      if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
-      if ((uintptr_t)src & (uintptr_t)(fmt_size(tr) - 1))
-        return fail(h, IPLS_E_INVAL, "device bucket not %d-byte aligned", fmt_size(tr));
-      dptr = src;
-      break;
-    case IPLS_HOST_F32:
-    case IPLS_HOST_F16:
-    case IPLS_HOST_BF16:
-      // 4 or 2 B per element cross PCIe; the widening happens on the device
-      tr = kind_fmt(src_kind);
-      if (int rc = host_decode_count(src_kind, n, L, h)) return rc;
-      if ((uintptr_t)src & (uintptr_t)(fmt_size(tr) - 1))
-        return fail(h, IPLS_E_INVAL, "host bucket not %d-byte aligned", fmt_size(tr));
-      if (int rc = stage_bucket(h, src, (size_t)L * fmt_size(tr), &dptr)) return rc;
-      staged = true;
-      break;
-    case IPLS_HOST_FRAME: {
-      int16_t pid;
-      int32_t a, b;
-      int64_t poff, ooff;
-      int64_t nd = ipls_frame_parse((const uint8_t*)src, n, &pid, &a, &b, &poff, &ooff);
-      if (nd < 0) return fail(h, IPLS_E_FORMAT, "malformed frame (BufferUnderflowException)");
-      if (nd == 0) return IPLS_OK;  // arr_len == 0 -> Gradients = null (MyIPFSClass.java:1449-1451)
-      if (int rc = host_decode_count(src_kind, nd, L, h)) return rc;
-      // The payload starts at byte 14 (unaligned); staging realigns it.
-      if (int rc = stage_bucket(h, (const char*)src + poff, (size_t)L * 8, &dptr)) return rc;
-      staged = true;
-      be = true;
-      break;
-    }
-    case IPLS_HOST_PAIR: {
-      // Download_Partial_Updates(hash).getValue1() -> queue -> _Update (Download_Scheduler.java:324)
-      int32_t workers;
-      int64_t poff;
-      const char* why = nullptr;
-      const int64_t nd = javaser::parse_pair((const uint8_t*)src, n, &workers, &poff, &why);
-      if (nd < 0) return fail(h, IPLS_E_FORMAT, "partial update: %s (ObjectInputStream)", why ? why : "malformed");
-      if (int rc = host_decode_count(src_kind, nd, L, h)) return rc;
-      if (int rc = stage_bucket(h, (const char*)src + poff, (size_t)L * 8, &dptr)) return rc;
-      staged = true;
-      be = true;
-      break;
-    }
-    case IPLS_HOST_DARR: {
-      // the single-partition hand-over file (MyIPFSClass.java:261-270), handled as the Pair's double[]
-      int64_t poff;
-      const char* why = nullptr;
-      const int64_t nd = javaser::parse_darr((const uint8_t*)src, n, &poff, &why);
-      if (nd < 0) return fail(h, IPLS_E_FORMAT, "serialised double[]: %s (ObjectInputStream)", why ? why : "malformed");
-      if (int rc = host_decode_count(src_kind, nd, L, h)) return rc;
-      if (int rc = stage_bucket(h, (const char*)src + poff, (size_t)L * 8, &dptr)) return rc;
-      staged = true;
-      be = true;
-      break;
-    }
-    default:
-      return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
+    // (a container's payload is unaligned, a frame's starts at byte 14: staging realigns it)
+    if (int rc = stage_bucket(h, v.ptr, bytes, &dptr)) return rc;
   }
   const void* bl[1] = {dptr};
-  if (int rc = reduce_dev(h, p, 1, bl, 1, fmt_trainer(tr) ? tr : be_fmt(be), IPLS_START_ACCUM, target, nullptr, false,
-                          nullptr, false, nullptr, /*arrival=*/true))
+  if (int rc = reduce_dev(h, p, 1, bl, 1, v.fmt, IPLS_START_ACCUM, target, nullptr, false, nullptr, false, nullptr,
+                          /*arrival=*/true))
     return rc;
-  return staged ? release_stage(h) : IPLS_OK;
+  return v.host ? release_stage(h) : IPLS_OK;
 }
 
 int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_t n, int src_kind,
                               uint64_t* ticket) {
   if (!h || !ticket) return fail(h, IPLS_E_INVAL, "null argument");
-  if (src && (src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE || kind_trainer_dev(src_kind))) {
+  op::Resolved v;
+  if (src && (op::kDev & op::bit(src_kind))) {
     // device bucket: queued, folded with the partition's other queued buckets
     // (a queue holds one format: a bucket of another one flushes first, so
     // call order is kept across F64, BE, F32, F16 and BF16 arrivals)
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = check_part(h, p)) return rc;
     if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
-    if (n < h->len[p])
-      return fail(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n,
-                  (long long)h->len[p]);
-    const Fmt fmt = kind_fmt(src_kind);
-    if ((uintptr_t)src & (uintptr_t)(fmt_size(fmt) - 1))
-      return fail(h, IPLS_E_INVAL, "device bucket not %d-byte aligned", fmt_size(fmt));
+    if (op::resolve(op::kAccumulateAsync, src, n, src_kind, h->len[p], &v) != op::kTake) return not_taken(h, v.why);
+    const Fmt fmt = v.fmt;
     // Weights and Weight_Address are one array (IPLS.java:1141): one queue
     const int qt = target == IPLS_TGT_WADDR ? IPLS_TGT_WEIGHTS : target;
     if (h->pend.empty()) h->pend.resize((size_t)5 * h->P);   // 5 targets (include/ipls_agg.h)
@@ -1395,8 +1336,8 @@ int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_
     return IPLS_OK;
   }
   void* alias = nullptr;
-  const bool host = src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE;
-  if (!src || !host || ((uintptr_t)src & 15) || !is_pinned_host(src, &alias) || !alias) {
+  const bool host = op::kHostD & op::bit(src_kind);
+  if (!src || !host || !op::zero_copy_queued(src) || !is_pinned_host(src, &alias) || !alias) {
     // not a pinned host bucket: the synchronous path, already complete on return
     int rc = dev_accumulate(h, p, target, src, n, src_kind);
     std::lock_guard<std::mutex> lk(h->mu);
@@ -1406,12 +1347,10 @@ int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_
   IPLS_LOCK(h);   // earlier queued device buckets fold first
   if (int rc = check_part(h, p)) return rc;
   if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
-  if (int rc = host_decode_count(src_kind, n, h->len[p], h)) return rc;
+  if (op::resolve(op::kAccumulateAsync, src, n, src_kind, h->len[p], &v) != op::kTake) return not_taken(h, v.why);
   HIP_TRY(h, dev_use(h->device));
   const void* bl[1] = {alias};   // zero copy: the kernel reads the pinned bucket over PCIe
-  if (int rc = reduce_dev(h, p, 1, bl, 1, be_fmt(src_kind == IPLS_HOST_BE), IPLS_START_ACCUM, target, nullptr, false, nullptr,
-                          true))
-    return rc;
+  if (int rc = reduce_dev(h, p, 1, bl, 1, v.fmt, IPLS_START_ACCUM, target, nullptr, false, nullptr, true)) return rc;
   *ticket = h->ticket_next++;
   return end_batch(h);
 }
@@ -1429,13 +1368,13 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
   IPLS_LOCK(h);   // earlier queued device buckets fold first
   if (int rc = check_part(h, p)) return rc;
   if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
-  if (src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE)
-    return fail(h, IPLS_E_INVAL, "a ranged fold reads a pinned host bucket (HOST_F64 / HOST_BE), not kind %d", src_kind);
   const int64_t L = h->len[p];
+  op::Resolved v;
+  if (op::resolve(op::kAccumulateRange, src, n, src_kind, L, &v) != op::kTake) return not_taken(h, v.why);
   if (off < 0 || n < 0 || off > L || n > L - off)
     return fail(h, IPLS_E_RANGE, "range [%lld, %lld) outside partition %d of length %lld", (long long)off,
                 (long long)(off + n), p, (long long)L);
-  if ((off & 1) || ((uintptr_t)src & 15))
+  if ((off & 1) || !op::zero_copy_queued(src))
     return fail(h, IPLS_E_INVAL, "a ranged fold needs an even start and 16-B aligned bytes");
   void* alias = nullptr;
   if (!is_pinned_host(src, &alias) || !alias)
@@ -1449,9 +1388,10 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
   unsigned long long* d0 = (unsigned long long*)(h->arena + target_off(h, p, target)) + off;
   const auto* s0 = (const unsigned long long*)alias;
   const unsigned blocks = std::max(1u, std::min<unsigned>(blocks_for(n >> 1, kBlock * 4), 128u));
-  const bool be = src_kind == IPLS_HOST_BE;
-  if (be) hipLaunchKernelGGL((k_fold1<true, false, kAccum>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, n);
-  else hipLaunchKernelGGL((k_fold1<false, false, kAccum>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, n);
+  const bool be = v.fmt == kFmtBE;
+  with_bool(be, [&](auto b) {
+    hipLaunchKernelGGL((k_fold1<decltype(b)::value, false, kAccum>), dim3(blocks), dim3(kBlock), 0, h->stream, d0, s0, n);
+  });
   HIP_TRY(h, hipGetLastError());
   h->last_launch = launch_info(IPLS_KERNEL_FOLD1, 0, kBlock, 4, 0, 0, blocks, be, false, IPLS_START_ACCUM);
   *ticket = h->ticket_next++;
@@ -1483,14 +1423,11 @@ static int accumulate_chunked_fmt(ipls_dev* h, int p, int target, int64_t n, int
   // offset is not read here: promote_future swaps AGG/FUT storage under it)
   if (p < 0 || p >= h->P) return fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", p, h->P);
   if (target < IPLS_TGT_AGG || target > IPLS_TGT_FUTURE) return fail_nl(h, IPLS_E_INVAL, "bad target %d", target);
-  if (narrow ? !kind_trainer_host(src_kind) : (src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE))
-    return fail_nl(h, IPLS_E_INVAL, "a %schunked fold takes %s values, not kind %d", narrow ? "narrow " : "",
-                   narrow ? "HOST_F32, HOST_F16 or HOST_BF16" : "HOST_F64 or HOST_BE", src_kind);
-  const Fmt fmt = kind_fmt(src_kind);
   const int64_t L = h->len[p];
-  if (n < L)   // before any source call (Updater.java:115)
-    return fail_nl(h, IPLS_E_RANGE, "bucket of %lld %s shorter than partition length %lld", (long long)n,
-                   fmt_trainer(fmt) ? "values" : "doubles", (long long)L);
+  op::Resolved v;   // the kind, and a short bucket before any source call (Updater.java:115)
+  if (op::resolve(narrow ? op::kChunkedNarrow : op::kChunked, nullptr, n, src_kind, L, &v) != op::kTake)
+    return fail_nl(h, v.why.code, "%s", v.why.text);
+  const Fmt fmt = v.fmt;
   HIP_TRY_NL(h, dev_use(h->device));
   const int64_t c = std::min(chunk, L);
   const size_t esz = (size_t)fmt_size(fmt);
@@ -1857,16 +1794,17 @@ int dev_read_range(ipls_dev* h, int p, int target, void* dst, int64_t off, int64
 static int gbuf_load(ipls_dev* h, const void* bytes, int64_t n_bytes, bool* zero_copy) {
   const int64_t G = h->gbuf_len;
   *zero_copy = false;
+  op::Resolved v;   // "bad byte buffer"
+  if (op::resolve(op::kUpdateIndirect, bytes, n_bytes, IPLS_HOST_BE, G, &v) != op::kTake) return not_taken(h, v.why);
   if (!h->d_gbuf) {
     HIP_TRY(h, hipMalloc(&h->d_gbuf, (size_t)std::max<int64_t>(G, 1) * 8));
     HIP_TRY(h, hipMemsetAsync(h->d_gbuf, 0, (size_t)std::max<int64_t>(G, 1) * 8, h->stream));
   }
-  const int64_t nd = n_bytes / 8;
-  const int64_t nw = std::min(nd, G);
+  const int64_t nd = v.n, nw = std::min(nd, G);
   if (nw > 0) {
     const void* dsrc = nullptr;
     void* alias = nullptr;
-    if (((uintptr_t)bytes & 7) == 0 && (size_t)nw * 8 >= (1u << 16) && is_pinned_host(bytes, &alias) && alias) {
+    if (op::zero_copy_arrival(bytes, (size_t)nw * 8) && is_pinned_host(bytes, &alias) && alias) {
       dsrc = alias;
       *zero_copy = true;
     } else {
@@ -1891,7 +1829,6 @@ int dev_update_indirect(ipls_dev* h, int p, int target, const void* bytes, int64
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
   if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
-  if (n_bytes < 0 || (n_bytes > 0 && !bytes)) return fail(h, IPLS_E_INVAL, "bad byte buffer");
   HIP_TRY(h, dev_use(h->device));
   const int64_t G = h->gbuf_len;
   bool zero_copy = false;
@@ -1913,7 +1850,6 @@ int dev_update_indirect(ipls_dev* h, int p, int target, const void* bytes, int64
 int dev_gbuf_load(ipls_dev* h, const void* bytes, int64_t n_bytes, const void** gbuf, int64_t* glen) {
   if (!h || !gbuf || !glen) return fail(h, IPLS_E_INVAL, "null argument");
   IPLS_LOCK(h);
-  if (n_bytes < 0 || (n_bytes > 0 && !bytes)) return fail(h, IPLS_E_INVAL, "bad byte buffer");
   HIP_TRY(h, dev_use(h->device));
   bool zero_copy = false;
   if (int rc = gbuf_load(h, bytes, n_bytes, &zero_copy)) return rc;
@@ -1982,12 +1918,8 @@ int dev_read(ipls_dev* h, int p, int target, void* dst, int64_t n, int dst_kind)
       launch_bswap(h->stream, (const unsigned long long*)srcd, (unsigned long long*)dst, L);
       HIP_TRY(h, hipGetLastError());
       return IPLS_OK;
-    case IPLS_HOST_BE: {
-      if (int rc = ensure_scratch(h, (size_t)L * 8)) return rc;
-      launch_bswap(h->stream, (const unsigned long long*)srcd, (unsigned long long*)h->d_scratch, L);
-      HIP_TRY(h, hipGetLastError());
-      return d2h(h, dst, h->d_scratch, (size_t)L * 8);
-    }
+    case IPLS_HOST_BE:
+      return be_to_host(h, dst, srcd, L);
     default:
       return fail(h, IPLS_E_INVAL, "bad dst_kind %d", dst_kind);
   }
@@ -2123,10 +2055,7 @@ int dev_finalize(ipls_dev* h, int p, void* sum_out, int sum_kind, double* avg_ou
       if (sum_kind == IPLS_HOST_F64) {
         if (int rc = d2h(h, sum_out, w, (size_t)L * 8)) return rc;
       } else if (sum_kind == IPLS_HOST_BE) {
-        if (int rc = ensure_scratch(h, (size_t)L * 8)) return rc;
-        launch_bswap(h->stream, (const unsigned long long*)w, (unsigned long long*)h->d_scratch, L);
-        HIP_TRY(h, hipGetLastError());
-        if (int rc = d2h(h, sum_out, h->d_scratch, (size_t)L * 8)) return rc;
+        if (int rc = be_to_host(h, sum_out, w, L)) return rc;
       } else {
         return fail(h, IPLS_E_INVAL, "sum_kind must be HOST_F64 or HOST_BE");
       }
@@ -2199,130 +2128,53 @@ int dev_set_weights(ipls_dev* h, int p, const void* src, int64_t n, int src_kind
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
   const int64_t L = h->len[p];
-  if (src_kind == IPLS_HOST_FRAME) {
-    // ThreadReceiver pid 4 (IPLS.java:491-498): Weight_Address[p][i] =
-    // GET_GRADIENTS(frame) payload[i] for i < L_p.
-    int16_t pid;
-    int32_t a, b;
-    int64_t poff, ooff;
-    const int64_t nd = ipls_frame_parse((const uint8_t*)src, n, &pid, &a, &b, &poff, &ooff);
-    if (nd < 0) return fail(h, IPLS_E_FORMAT, "malformed frame (BufferUnderflowException)");
-    if (nd == 0) return fail(h, IPLS_E_INVAL, "frame without gradients (NullPointerException, IPLS.java:498)");
-    if (nd < L)
-      return fail(h, IPLS_E_RANGE, "frame payload of %lld doubles < length %lld (IPLS.java:498)", (long long)nd,
-                  (long long)L);
-    HIP_TRY(h, dev_use(h->device));
-    if (int rc = ensure_scratch(h, (size_t)L * 8)) return rc;
-    if (int rc = stage_h2d(h, h->d_scratch, (const char*)src + poff, (size_t)L * 8)) return rc;
-    launch_bswap(h->stream, (const unsigned long long*)h->d_scratch, (unsigned long long*)(h->arena + h->w_off[p]), L);
-    HIP_TRY(h, hipGetLastError());
+  op::Resolved v;
+  if (op::resolve(op::kSetWeights, src, n, src_kind, L, &v) != op::kTake) return not_taken(h, v.why);
+  HIP_TRY(h, dev_use(h->device));
+  // ThreadReceiver pid 4 (IPLS.java:491-498): Weight_Address[p][i] = GET_GRADIENTS(frame) payload[i] for
+  // i < L_p.  GetParameters(hash, arr) writes all its data.length / 8 values (MyIPFSClass.java:449-452).
+  const int64_t m = v.from == op::kFrame ? L : v.n;
+  double* w = h->arena + h->w_off[p];
+  const void* d = v.ptr;
+  if (v.host) {
+    if (v.fmt == kFmtF64) return stage_h2d(h, w, v.ptr, (size_t)m * 8);
+    if (int rc = to_scratch(h, v.ptr, (size_t)m * 8)) return rc;
+    d = h->d_scratch;
+  } else if (v.fmt == kFmtF64) {
+    HIP_TRY(h, hipMemcpyAsync(w, v.ptr, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
     return IPLS_OK;
   }
-  if (src_kind == IPLS_HOST_DARR) {   // the array's big-endian payload, then as HOST_BE
-    int64_t poff;
-    const char* why = nullptr;
-    const int64_t nd = javaser::parse_darr((const uint8_t*)src, n, &poff, &why);
-    if (nd < 0) return fail(h, IPLS_E_FORMAT, "serialised double[]: %s (ObjectInputStream)", why ? why : "malformed");
-    src = (const char*)src + poff;
-    n = nd;
-    src_kind = IPLS_HOST_BE;
-  }
-  // GetParameters(hash, arr) writes data.length/8 values (MyIPFSClass.java:449-452);
-  // more than arr.length -> ArrayIndexOutOfBoundsException.
-  if (n > L) return fail(h, IPLS_E_RANGE, "downloaded partition of %lld doubles > length %lld", (long long)n, (long long)L);
-  if (n <= 0) return IPLS_OK;
-  HIP_TRY(h, dev_use(h->device));
-  double* w = h->arena + h->w_off[p];
-  switch (src_kind) {
-    case IPLS_HOST_F64:
-      return stage_h2d(h, w, src, (size_t)n * 8);
-    case IPLS_HOST_BE: {
-      if (int rc = ensure_scratch(h, (size_t)n * 8)) return rc;
-      if (int rc = stage_h2d(h, h->d_scratch, src, (size_t)n * 8)) return rc;
-      launch_bswap(h->stream, (const unsigned long long*)h->d_scratch, (unsigned long long*)w, n);
-      HIP_TRY(h, hipGetLastError());
-      return IPLS_OK;
-    }
-    case IPLS_DEV_F64:
-      HIP_TRY(h, hipMemcpyAsync(w, src, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
-      return IPLS_OK;
-    case IPLS_DEV_BE:
-      launch_bswap(h->stream, (const unsigned long long*)src, (unsigned long long*)w, n);
-      HIP_TRY(h, hipGetLastError());
-      return IPLS_OK;
-    default:
-      return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
-  }
+  launch_bswap(h->stream, (const unsigned long long*)d, (unsigned long long*)w, m);
+  HIP_TRY(h, hipGetLastError());
+  return IPLS_OK;
 }
 
-// Bring a flat vector of n doubles (host or device, native or BE) onto the
-// device; returns a device pointer and whether it is big-endian.
-static int flat_to_device(ipls_dev* h, const void* flat, int64_t n, int kind, const unsigned long long** d,
-                          bool* be) {
-  switch (kind) {
-    case IPLS_DEV_F64:
-    case IPLS_DEV_BE:
-      *d = (const unsigned long long*)flat;
-      *be = kind == IPLS_DEV_BE;
-      return IPLS_OK;
-    case IPLS_HOST_F64:
-    case IPLS_HOST_BE:
-      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(n, 1) * 8)) return rc;
-      if (n > 0)
-        if (int rc = stage_h2d(h, h->d_scratch, flat, (size_t)n * 8)) return rc;
-      *d = (const unsigned long long*)h->d_scratch;
-      *be = kind == IPLS_HOST_BE;
-      return IPLS_OK;
-    // trainer-format vectors (update_gradient / load_model only reach here
-    // with them): *d then points at floats, halves or bfloat16s, 4 or 2 B per
-    // element on the device and over PCIe
-    case IPLS_DEV_F32:
-    case IPLS_DEV_F16:
-    case IPLS_DEV_BF16: {
-      const int esz = fmt_size(kind_fmt(kind));
-      if ((uintptr_t)flat & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "device vector not %d-byte aligned", esz);
-      *d = (const unsigned long long*)flat;
-      *be = false;
-      return IPLS_OK;
-    }
-    case IPLS_HOST_F32:
-    case IPLS_HOST_F16:
-    case IPLS_HOST_BF16: {
-      const int esz = fmt_size(kind_fmt(kind));
-      if ((uintptr_t)flat & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "host vector not %d-byte aligned", esz);
-      if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(n, 1) * esz)) return rc;
-      if (n > 0)
-        if (int rc = stage_h2d(h, h->d_scratch, flat, (size_t)n * esz)) return rc;
-      *d = (const unsigned long long*)h->d_scratch;
-      *be = false;
-      return IPLS_OK;
-    }
-    default:
-      return fail(h, IPLS_E_INVAL, "bad flat kind %d", kind);
-  }
+// A resolved flat vector (doubles, or a trainer format at 4 or 2 B per element
+// on the device and over PCIe) as device memory: one of host memory goes
+// through the scratch buffer, one of device memory is used in place.
+static int flat_to_device(ipls_dev* h, const op::SrcView& v, const unsigned long long** d) {
+  *d = (const unsigned long long*)v.ptr;
+  if (!v.host) return IPLS_OK;
+  if (int rc = to_scratch(h, v.ptr, (size_t)v.n * fmt_size(v.fmt))) return rc;
+  *d = (const unsigned long long*)h->d_scratch;
+  return IPLS_OK;
 }
 
 int dev_other_replica(ipls_dev* h, int p, int32_t aggregator, const void* src, int64_t n, int src_kind) {
   if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
-  if (n < 0 || (n > 0 && !src)) return fail(h, IPLS_E_INVAL, "bad bucket");
-  if (kind_trainer(src_kind)) return fail(h, IPLS_E_INVAL, "bad flat kind %d", src_kind);
-  if ((src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE) && ((uintptr_t)src & 7))
-    return fail(h, IPLS_E_INVAL, "device bucket not 8-byte aligned");
-  HIP_TRY(h, dev_use(h->device));
   auto key = std::make_pair(p, aggregator);
   auto it = h->other.find(key);
   const bool first = it == h->other.end();
   // Download_Scheduler.java:254-260: `for j < gradients.length: Other[j] += g[j]`
   // -- a longer download overruns the stored array (rejected before folding).
-  if (!first && n > it->second.n)
-    return fail(h, IPLS_E_RANGE, "replica download of %lld doubles > stored %lld "
-                "(ArrayIndexOutOfBoundsException, Download_Scheduler.java:257)", (long long)n,
-                (long long)it->second.n);
+  op::Resolved v;
+  if (op::resolve(op::kOtherReplica, src, n, src_kind, first ? -1 : it->second.n, &v) != op::kTake) return not_taken(h, v.why);
+  HIP_TRY(h, dev_use(h->device));
   const unsigned long long* d;
-  bool be;
-  if (int rc = flat_to_device(h, src, n, src_kind, &d, &be)) return rc;
+  const bool be = v.fmt == kFmtBE;
+  if (int rc = flat_to_device(h, v, &d)) return rc;
   unsigned long long* dst = first ? nullptr : it->second.d;
   // Other.put(key, GetParameters(Hash)): a new array of the file's length (:263)
   if (first) HIP_TRY(h, hipMalloc(&dst, (size_t)std::max<int64_t>(n, 1) * 8));
@@ -2340,7 +2192,7 @@ int dev_other_replica(ipls_dev* h, int p, int32_t aggregator, const void* src, i
     });
     e = hipGetLastError();
   }
-  if (e == hipSuccess && (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE)) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess && v.host) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {   // the store is left as it was (the front's key model relies on it)
     (void)hipGetLastError();
     if (first) hipFree(dst);
@@ -2409,12 +2261,10 @@ int dev_collect_replicas(ipls_dev* h, int32_t* participants, const int32_t* orde
       if (int rc = materialize(h, p, IPLS_TGT_REP)) return rc;
       auto rdst = (unsigned long long*)(h->arena + h->rep_off[p]);
       const bool vec = al16(rdst) && al16(it->second.d);
-      if (vec)
-        hipLaunchKernelGGL((k_fold_n<false, false, true>), ew_grid(n, true, 4096), dim3(kBlock), 0, h->stream, rdst,
-                           it->second.d, n);
-      else
-        hipLaunchKernelGGL((k_fold_n<false, false, false>), ew_grid(n, false, 4096), dim3(kBlock), 0, h->stream,
+      with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((k_fold_n<false, false, decltype(v)::value>), ew_grid(n, vec, 4096), dim3(kBlock), 0, h->stream,
                            rdst, it->second.d, n);
+      });
       HIP_TRY(h, hipGetLastError());
     }
     ++folded;
@@ -2429,16 +2279,15 @@ int dev_collect_replicas(ipls_dev* h, int32_t* participants, const int32_t* orde
 int dev_load_model(ipls_dev* h, const void* src, int64_t n, int src_kind) {
   if (!h || !src) return fail(h, IPLS_E_INVAL, "null argument");
   IPLS_LOCK(h);
-  if (n < h->flat_total)
-    return fail(h, IPLS_E_RANGE, "model of %lld values < model size %lld", (long long)n, (long long)h->flat_total);
+  op::Resolved v;
+  if (op::resolve(op::kLoadModel, src, n, src_kind, h->flat_total, &v) != op::kTake) return not_taken(h, v.why);
   HIP_TRY(h, dev_use(h->device));
   const unsigned long long* d;
-  bool be;
-  const Fmt fmt = kind_fmt(src_kind);
+  const Fmt fmt = v.fmt;
   // only this engine's segment [flat_base, flat_total) of the model
-  if (int rc = flat_to_device(h, (const char*)src + fmt_size(fmt) * h->flat_base, h->flat_total - h->flat_base,
-                              src_kind, &d, &be))
-    return rc;
+  v.ptr = (const char*)v.ptr + fmt_size(fmt) * h->flat_base;
+  v.n = h->flat_total - h->flat_base;
+  if (int rc = flat_to_device(h, v, &d)) return rc;
   for (int p = 0; p < h->P; ++p) {
     const int64_t L = h->len[p];
     // IPLS.java:1883-1895: values for j < min((i+1)c, M), count slot 0.0
@@ -2449,12 +2298,11 @@ int dev_load_model(ipls_dev* h, const void* src, int64_t n, int src_kind) {
                            (const typename S::elem*)d, h->flat_off[p] - h->flat_base, L - 1, L,
                            h->arena + h->w_off[p]);
       });
-    else if (be)
-      hipLaunchKernelGGL(k_load_model<true>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, d,
-                         h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
     else
-      hipLaunchKernelGGL(k_load_model<false>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, d,
-                         h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+      with_bool(fmt == kFmtBE, [&](auto be) {
+        hipLaunchKernelGGL(k_load_model<decltype(be)::value>, dim3(blocks_for(L, kBlock)), dim3(kBlock), 0, h->stream, d,
+                           h->flat_off[p] - h->flat_base, L - 1, L, h->arena + h->w_off[p]);
+      });
     HIP_TRY(h, hipGetLastError());
     h->agg_zero[p] = h->rep_zero[p] = h->fut_zero[p] = 1;   // IPLS.java:1886-1898
   }
@@ -2482,47 +2330,26 @@ int dev_split(ipls_dev* h, const void* flat, int64_t n, int src_kind, int p, voi
   if (int rc = split_bounds(h, p, n, &ncopy)) return rc;
   HIP_TRY(h, dev_use(h->device));
   const int64_t L = h->len[p];
-  const unsigned long long* d;
-  bool be_in;
-  // only the partition's own slice is needed on the device
-  const int64_t lo = h->flat_off[p];
-  const Fmt fmt = kind_trainer(src_kind) ? kind_fmt(src_kind) : kFmtF64;
-  if (fmt_trainer(fmt)) {
-    // floats, halves or bfloat16s: 4 or 2 B per element; a host slice is
-    // staged into the first L + 1 doubles' worth of scratch (it needs a half
-    // or a quarter of that), the output after it
-    const int esz = fmt_size(fmt);
-    if ((uintptr_t)flat & (uintptr_t)(esz - 1)) return fail(h, IPLS_E_INVAL, "vector not %d-byte aligned", esz);
-    if (int rc = ensure_scratch(h, (size_t)(2 * L + 2) * 8)) return rc;
-    if (kind_trainer_host(src_kind)) {
-      if (ncopy > 0)
-        if (int rc = stage_h2d(h, h->d_scratch, (const char*)flat + lo * esz, (size_t)ncopy * esz)) return rc;
-      d = (const unsigned long long*)h->d_scratch;
-    } else {
-      d = (const unsigned long long*)((const char*)flat + lo * esz);
-    }
-    be_in = false;
-  } else if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
-    if (int rc = ensure_scratch(h, (size_t)(2 * L + 2) * 8)) return rc;
-    if (ncopy > 0)
-      if (int rc = stage_h2d(h, h->d_scratch, (const char*)flat + lo * 8, (size_t)ncopy * 8)) return rc;
-    d = (const unsigned long long*)h->d_scratch;
-    be_in = src_kind == IPLS_HOST_BE;
-  } else if (src_kind == IPLS_DEV_F64 || src_kind == IPLS_DEV_BE) {
-    d = (const unsigned long long*)flat + lo;
-    be_in = src_kind == IPLS_DEV_BE;
-    if (int rc = ensure_scratch(h, (size_t)(L + 1) * 8)) return rc;
-  } else {
-    return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
-  }
+  op::Resolved sv;
+  if (op::resolve(op::kSplit, flat, n, src_kind, L, &sv) != op::kTake) return not_taken(h, sv.why);
+  // only the partition's own slice is needed on the device (doubles, or
+  // floats, halves or bfloat16s at 4 or 2 B per element): a host slice is
+  // staged into the first L + 1 doubles' worth of scratch, the output after it
+  const Fmt fmt = fmt_trainer(sv.fmt) ? sv.fmt : kFmtF64;
+  const bool be_in = sv.fmt == kFmtBE;
+  const int esz = fmt_size(fmt);
+  const char* slice = (const char*)flat + h->flat_off[p] * esz;
+  if (int rc = sv.host ? to_scratch(h, slice, (size_t)ncopy * esz, (size_t)(2 * L + 2) * 8)
+                      : ensure_scratch(h, (size_t)(fmt_trainer(fmt) ? 2 * L + 2 : L + 1) * 8))
+    return rc;
+  const auto* d = (const unsigned long long*)(sv.host ? (const char*)h->d_scratch : slice);
   const bool host_out = dst_kind == IPLS_HOST_F64 || dst_kind == IPLS_HOST_BE;
   const bool be_out = dst_kind == IPLS_HOST_BE || dst_kind == IPLS_DEV_BE;
   if (!host_out && dst_kind != IPLS_DEV_F64 && dst_kind != IPLS_DEV_BE)
     return fail(h, IPLS_E_INVAL, "bad dst_kind %d", dst_kind);
   unsigned long long* out = host_out ? (unsigned long long*)((char*)h->d_scratch + (size_t)(L + 1) * 8)
                                      : (unsigned long long*)dst;
-  if (host_out && src_kind != IPLS_HOST_F64 && src_kind != IPLS_HOST_BE && !kind_trainer_host(src_kind))
-    out = (unsigned long long*)h->d_scratch;
+  if (host_out && !sv.host) out = (unsigned long long*)h->d_scratch;
   const bool vec = al16(d) && al16(out);
   const dim3 g = vec ? dim3(std::max(1u, blocks_for(L, kEwTile))) : dim3(blocks_for(L, kBlock));
   auto flags = [&](auto&& f) {   // f(be_out, vec)
@@ -2563,29 +2390,25 @@ int dev_update_gradient(ipls_dev* h, const void* flat, int64_t n, int src_kind, 
     if (int rc = check_part(h, owned[i])) return rc;
   if (n_owned == 0) return IPLS_OK;
   HIP_TRY(h, dev_use(h->device));
-  const unsigned long long* d;
-  bool be;
+  op::Resolved sv;
+  if (op::resolve(op::kUpdateGradient, flat, n, src_kind, 0, &sv) != op::kTake) return not_taken(h, sv.why);
   // only this engine's segment of the gradient vector (flat_base on)
   const int64_t seg = std::max<int64_t>(0, std::min(n, h->flat_total) - h->flat_base);
-  const Fmt fmt = kind_trainer(src_kind) ? kind_fmt(src_kind) : kFmtF64;
+  const Fmt fmt = fmt_trainer(sv.fmt) ? sv.fmt : kFmtF64;
+  const bool be = sv.fmt == kFmtBE;
   const int64_t esz = fmt_size(fmt);
-  if (kind_trainer_host(src_kind) || src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
+  const char* base = (const char*)flat + esz * h->flat_base;
+  auto d = (const unsigned long long*)base;   // device memory is read in place
+  if (sv.host) {
     // from host memory only the owned partitions' values cross PCIe, at 8, 4
     // or 2 B per element: the others are split by OrganizeGradients too, but
     // never accumulated (IPLS.java:1737-1743), so their bytes are never read here
-    if (fmt_trainer(fmt) && ((uintptr_t)flat & (uintptr_t)(esz - 1)))
-      return fail(h, IPLS_E_INVAL, "host vector not %d-byte aligned", (int)esz);
     if (int rc = ensure_scratch(h, (size_t)std::max<int64_t>(seg, 1) * esz)) return rc;
-    const char* base = (const char*)flat + esz * h->flat_base;
     for (int i = 0; i < n_owned; ++i) {
       const int64_t lo = h->flat_off[owned[i]] - h->flat_base;
-      if (nc[owned[i]] > 0)
-        if (int rc = stage_h2d(h, (char*)h->d_scratch + esz * lo, base + esz * lo, (size_t)nc[owned[i]] * esz)) return rc;
+      if (int rc = stage_h2d(h, (char*)h->d_scratch + esz * lo, base + esz * lo, (size_t)nc[owned[i]] * esz)) return rc;
     }
     d = (const unsigned long long*)h->d_scratch;
-    be = src_kind == IPLS_HOST_BE;
-  } else if (int rc = flat_to_device(h, (const char*)flat + esz * h->flat_base, seg, src_kind, &d, &be)) {
-    return rc;
   }
   for (int i = 0; i < n_owned; ++i) {
     const int p = owned[i];
@@ -3047,40 +2870,22 @@ int dev_blend(ipls_dev* h, int p, int target, const void* src, int64_t n, int sr
   IPLS_LOCK(h);
   if (int rc = check_part(h, p)) return rc;
   if (target_off(h, p, target) < 0) return fail(h, IPLS_E_INVAL, "bad target %d", target);
-  if (!src) return IPLS_OK;
   const int64_t L = h->len[p];
-  if (src_kind == IPLS_HOST_DARR) {   // the array's big-endian payload, then as HOST_BE
-    int64_t poff;
-    const char* why = nullptr;
-    const int64_t nd = javaser::parse_darr((const uint8_t*)src, n, &poff, &why);
-    if (nd < 0) return fail(h, IPLS_E_FORMAT, "serialised double[]: %s (ObjectInputStream)", why ? why : "malformed");
-    src = (const char*)src + poff;
-    n = nd;
-    src_kind = IPLS_HOST_BE;
-  }
-  if (n < L) return fail(h, IPLS_E_RANGE, "bucket of %lld doubles shorter than partition length %lld", (long long)n, (long long)L);
+  op::Resolved v;   // HOST_DARR: the array's big-endian payload, then as HOST_BE
+  if (op::resolve(op::kBlend, src, n, src_kind, L, &v) != op::kTake) return not_taken(h, v.why);
   HIP_TRY(h, dev_use(h->device));
-  const void* d = src;
-  bool be = src_kind == IPLS_HOST_BE || src_kind == IPLS_DEV_BE;
-  if (src_kind == IPLS_HOST_F64 || src_kind == IPLS_HOST_BE) {
-    if (int rc = ensure_scratch(h, (size_t)L * 8)) return rc;
-    if (int rc = stage_h2d(h, h->d_scratch, src, (size_t)L * 8)) return rc;
-    d = h->d_scratch;
-  } else if (src_kind != IPLS_DEV_F64 && src_kind != IPLS_DEV_BE) {
-    return fail(h, IPLS_E_INVAL, "bad src_kind %d", src_kind);
-  }
+  if (v.host)
+    if (int rc = to_scratch(h, v.ptr, (size_t)L * 8)) return rc;
+  auto gs = (const unsigned long long*)(v.host ? h->d_scratch : v.ptr);
   if (int rc = materialize(h, p, target)) return rc;
   double* t = h->arena + target_off(h, p, target);
-  const bool vec = al16(t) && al16(d);
+  const bool vec = al16(t) && al16(gs);
   const dim3 g = ew_grid(L, vec, 8192);
-  auto gs = (const unsigned long long*)d;
-  if (be) {
-    if (vec) hipLaunchKernelGGL((k_blend<true, true>), g, dim3(kBlock), 0, h->stream, t, gs, L, a, b);
-    else hipLaunchKernelGGL((k_blend<true, false>), g, dim3(kBlock), 0, h->stream, t, gs, L, a, b);
-  } else {
-    if (vec) hipLaunchKernelGGL((k_blend<false, true>), g, dim3(kBlock), 0, h->stream, t, gs, L, a, b);
-    else hipLaunchKernelGGL((k_blend<false, false>), g, dim3(kBlock), 0, h->stream, t, gs, L, a, b);
-  }
+  with_bool(v.fmt == kFmtBE, [&](auto be) {
+    with_bool(vec, [&](auto vc) {
+      hipLaunchKernelGGL((k_blend<decltype(be)::value, decltype(vc)::value>), g, dim3(kBlock), 0, h->stream, t, gs, L, a, b);
+    });
+  });
   HIP_TRY(h, hipGetLastError());
   return IPLS_OK;
 }
@@ -3096,10 +2901,10 @@ int dev_scale(ipls_dev* h, int p, int dst_target, int src_target, double c) {
   const int64_t L = h->len[p];
   double* sd = h->arena + target_off(h, p, dst_target);
   auto ss = (const double*)(h->arena + target_off(h, p, src_target));
-  if (al16(sd) && al16(ss))
-    hipLaunchKernelGGL(k_scale<true>, ew_grid(L, true, 8192), dim3(kBlock), 0, h->stream, sd, ss, L, c);
-  else
-    hipLaunchKernelGGL(k_scale<false>, ew_grid(L, false, 8192), dim3(kBlock), 0, h->stream, sd, ss, L, c);
+  with_bool(al16(sd) && al16(ss), [&](auto v) {
+    hipLaunchKernelGGL(k_scale<decltype(v)::value>, ew_grid(L, decltype(v)::value, 8192), dim3(kBlock), 0, h->stream, sd, ss,
+                       L, c);
+  });
   HIP_TRY(h, hipGetLastError());
   return IPLS_OK;
 }
@@ -3343,10 +3148,7 @@ int64_t dev_commit_partial(ipls_dev* h, int p, int32_t workers, uint8_t* out, in
   if (h->agg_zero[p]) {
     std::memset(out + hl, 0, (size_t)L * 8);   // +0.0 in any byte order
   } else {
-    if (int rc = ensure_scratch(h, (size_t)L * 8)) return rc;
-    launch_bswap(h->stream, (const unsigned long long*)(h->arena + h->agg_off[p]), (unsigned long long*)h->d_scratch, L);
-    HIP_TRY(h, hipGetLastError());
-    if (int rc = d2h(h, out + hl, h->d_scratch, (size_t)L * 8)) return rc;
+    if (int rc = be_to_host(h, out + hl, h->arena + h->agg_off[p], L)) return rc;
   }
   javaser::write_pair_trailer(out + hl + 8 * L);
   return total;
@@ -3392,26 +3194,21 @@ int64_t dev_merge_files(ipls_dev* h, const uint8_t* const* files, const int64_t*
   }
   for (int i = 0; i < k; ++i) {
     if (nd[i] == 0) continue;
-    if (int rc = ensure_scratch(h, (size_t)nd[i] * 8)) return rc;
-    if (int rc = stage_h2d(h, h->d_scratch, files[i] + off[i], (size_t)nd[i] * 8)) return rc;
+    if (int rc = to_scratch(h, files[i] + off[i], (size_t)nd[i] * 8)) return rc;
     // (both device buffers come from hipMalloc: the tile shape)
     const bool vec = al16(h->d_merge) && al16(h->d_scratch);
     const dim3 g = ew_grid(nd[i], vec, 4096);
     auto msrc = (const unsigned long long*)h->d_scratch;
-    if (i == 0) {   // Aggregation = GetParameters(Hashes.get(0)): the first file as is
-      if (vec) hipLaunchKernelGGL((k_fold_n<true, true, true>), g, dim3(kBlock), 0, h->stream, h->d_merge, msrc, nd[i]);
-      else hipLaunchKernelGGL((k_fold_n<true, true, false>), g, dim3(kBlock), 0, h->stream, h->d_merge, msrc, nd[i]);
-    } else {
-      if (vec) hipLaunchKernelGGL((k_fold_n<true, false, true>), g, dim3(kBlock), 0, h->stream, h->d_merge, msrc, nd[i]);
-      else hipLaunchKernelGGL((k_fold_n<true, false, false>), g, dim3(kBlock), 0, h->stream, h->d_merge, msrc, nd[i]);
-    }
+    with_bool(i == 0, [&](auto first) {   // Aggregation = GetParameters(Hashes.get(0)): the first file as is
+      with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((k_fold_n<true, decltype(first)::value, decltype(v)::value>), g, dim3(kBlock), 0, h->stream,
+                           h->d_merge, msrc, nd[i]);
+      });
+    });
     HIP_TRY(h, hipGetLastError());
   }
   // update_file(..., Aggregation): putDouble per element (MyIPFSClass.java:105-116)
-  if (int rc = ensure_scratch(h, (size_t)n0 * 8)) return rc;
-  launch_bswap(h->stream, (const unsigned long long*)h->d_merge, (unsigned long long*)h->d_scratch, n0);
-  HIP_TRY(h, hipGetLastError());
-  if (int rc = d2h(h, out, h->d_scratch, (size_t)n0 * 8)) return rc;
+  if (int rc = be_to_host(h, out, h->d_merge, n0)) return rc;
   return 8 * n0;
 }
 
@@ -3669,8 +3466,7 @@ int dev_ser_apply(ipls_dev* h, const uint8_t* bytes, int64_t lo, int64_t hi, con
     max_pairs = std::max(max_pairs, L / 2 + 1);
   }
   HIP_TRY(h, dev_use(h->device));
-  if (int rc = ensure_scratch(h, (size_t)(hi - lo) + 32)) return rc;
-  if (int rc = stage_h2d(h, h->d_scratch, bytes + lo, (size_t)(hi - lo))) return rc;
+  if (int rc = to_scratch(h, bytes + lo, (size_t)(hi - lo), (size_t)(hi - lo) + 32)) return rc;
   for (int i = 0; i < n; ++i) {
     if (mode == IPLS_SAVED_BLEND) {
       if (int rc = materialize(h, q[i], target)) return rc;
