@@ -774,6 +774,53 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
                                   const int32_t *b, int16_t pid, const uint8_t *origin, int32_t origin_len,
                                   void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
 
+/* ---- send-side codec ----
+ * The sender's half of a round: every peer is a client for the partitions it
+ * does not own and sends each of them its slice of the gradient, every round.
+ * Text i is produced on the device straight from the flat vector
+ * (k_b64url_encode_flat, one launch per GPU): no split to host doubles, no
+ * host frame, no host base64 pass.
+ *
+ * The frame is [i16 pid][i32 L_p][i32 parts[i]][i32 iteration][L_p x f64 BE]
+ * [origin].  With lo = the partition's flat offset and ncopy = the values of
+ * flat that fall into it (OrganizeGradients, IPLS.java:1018-1040), payload
+ * value j is
+ *   (double)flat[lo + j]  for j < ncopy: the widening rules of the F32 / F16 /
+ *                         BF16 kinds above; doubles pass bit for bit (HOST_BE /
+ *                         DEV_BE: their bytes as they are);
+ *   1.0                   at j == ncopy, the count slot (IPLS.java:1033);
+ *   +0.0                  for ncopy < j < L_p (a vector shorter than the model).
+ * No addition is made anywhere: putDouble writes raw bits, so a -0.0 value is
+ * -0.0 in the text (unlike ipls_agg_update_gradient, whose +0.0 + -0.0 is
+ * +0.0), and a NaN keeps its payload.
+ *
+ * src_kind: exactly the kinds of ipls_agg_split (HOST / DEV x F64, BE, F32,
+ * F16, BF16), with its refusals; from host memory only the bytes from the
+ * first listed partition's first value to the last one's last value cross
+ * PCIe.  As in OrganizeGradients every partition of the model is bounded
+ * first: a vector that overruns any partition is IPLS_E_RANGE before anything
+ * is written, and so is a listed index outside [0, P).  flat == NULL is the
+ * "did not train in time" send (IPLS.java:1306-1312): every text is
+ * Marshall_Packet(null, ...), n = 0, the header and the origin.
+ *
+ * The text is ONE base64 layer, what Marshall_Packet returns; the second layer
+ * that receivers undo first (ipls_agg_ingest_pubsub, layers = 2) is the pubsub
+ * transport's own.  Secure mode's Middleware.Encode is not applied: a secure
+ * caller encodes before it sends (ipls_encode_secure), as Middleware.java:242-
+ * 244 does before UpdateModel.
+ *
+ * The call reads and writes no accumulator and does not fold queued
+ * asynchronous arrivals.  Text layout, out == NULL (sizes only), lens / offs,
+ * the 64-byte text offsets, out_kind and stream ordering: as
+ * ipls_agg_publish_partials.  IPLS_DEV_TEXT or a DEV source with partitions
+ * on several GPUs: memory every owner device can reach. */
+/* SendGradients (IPLS.java:1350-1400 -> Send_Gradient_Partition :1290-1322, direct mode): text i =
+ * Base64.getUrlEncoder(Marshall_Packet(OrganizeGradients(flat)[parts[i]], origin, parts[i], iteration, pid)) */
+int64_t ipls_agg_send_gradients(ipls_agg *h, const void *flat, int64_t n, int src_kind,
+                                const int32_t *parts, int n_parts, int32_t iteration, int16_t pid,
+                                const uint8_t *origin, int32_t origin_len,
+                                void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
+
 /* ---- observability ----
  * What the last fold launch of a handle (of p's shard for multi-GPU handles:
  * the shard of the last call) ran: the kernel, the tile shape chosen by the
@@ -802,6 +849,11 @@ int64_t ipls_agg_publish_partials(ipls_agg *h, const int32_t *parts, int n_parts
                                         trainer-format elements; grid = blocks x jobs; shape 0; seqf 1 when
                                         every job had a full tile of values (the vector body), else 0; start
                                         ZERO when every job's accumulator was logically zero, else ACCUM */
+#define IPLS_KERNEL_ENCODE_FLAT  12  /* k_b64url_encode_flat (send_gradients): one launch over a shard's listed
+                                        partitions; a lane writes the 32 chars of 24 frame bytes, a fast lane from
+                                        `vectors` = 4 source elements; grid = blocks x jobs; shape 0; seqf 1 when
+                                        at least one lane of one job took the fast path, else 0; be_in as for the
+                                        fold kernels */
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2
 #define IPLS_SHAPE_SMALL  3

@@ -3377,6 +3377,152 @@ int64_t dev_publish_many(ipls_dev* h, int n, const int* parts, int target, int32
   return IPLS_OK;
 }
 
+// ---- SendGradients: a flat gradient's partitions as pubsub texts (k_b64url_encode_flat) ----
+// IPLS.java:1350-1400 -> Send_Gradient_Partition (:1290-1322, direct mode): for every partition the peer does not
+// own, Marshall_Packet(OrganizeGradients(g)[p], id, p, middleware_iteration, 3) under Base64.getUrlEncoder.  One
+// launch reads the listed partitions' values where they lie in the flat vector (doubles, big-endian doubles or a
+// trainer format, at any element offset), generates the count slot and the zero tail, and writes the texts: no
+// split to host doubles, no host frame, no host base64 pass.
+namespace {
+void frame_header(unsigned char* hdr, int16_t pid, int64_t n, int32_t a, int32_t b) {
+  const uint32_t hv[3] = {(uint32_t)n, (uint32_t)a, (uint32_t)b};
+  hdr[0] = (unsigned char)((uint16_t)pid >> 8);        // putShort(0, pid)
+  hdr[1] = (unsigned char)pid;
+  for (int f = 0; f < 3; ++f)                          // putInt(2 | 6 | 10, ...)
+    for (int k = 0; k < 4; ++k) hdr[2 + 4 * f + k] = (unsigned char)(hv[f] >> (24 - 8 * k));
+}
+// Base64.getUrlEncoder ('=' padding) of n bytes on the host: the 14-byte frames of a null gradient
+void b64url_host(const unsigned char* in, int64_t n, unsigned char* out) {
+  static const char tab[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789-_";
+  for (int64_t i = 0; i < n; i += 3, out += 4) {
+    const int nb = n - i >= 3 ? 3 : (int)(n - i);
+    const unsigned v = (unsigned)in[i] << 16 | (nb > 1 ? (unsigned)in[i + 1] << 8 : 0u) | (nb > 2 ? (unsigned)in[i + 2] : 0u);
+    out[0] = (unsigned char)tab[v >> 18];
+    out[1] = (unsigned char)tab[(v >> 12) & 63];
+    out[2] = nb > 1 ? (unsigned char)tab[(v >> 6) & 63] : (unsigned char)'=';
+    out[3] = nb > 2 ? (unsigned char)tab[v & 63] : (unsigned char)'=';
+  }
+}
+}  // namespace
+
+int64_t dev_send_many(ipls_dev* h, const void* flat, int64_t n, int src_kind, int n_parts, const int* parts,
+                      int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
+                      const int64_t* offs, const int64_t* lens, int out_kind) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  // the shard's scratch buffer and stream; no accumulator, zero flag or queue is read or written, so queued
+  // arrivals stay queued (no IPLS_LOCK flush)
+  std::lock_guard<std::mutex> lk_(h->mu);
+  if (n_parts <= 0) return IPLS_OK;
+  if (origin_len < 0 || (origin_len > 0 && !origin)) return fail(h, IPLS_E_INVAL, "bad origin");
+  if (out_kind != IPLS_HOST_TEXT && out_kind != IPLS_DEV_TEXT) return fail(h, IPLS_E_INVAL, "out_kind HOST_TEXT/DEV_TEXT");
+  for (int i = 0; i < n_parts; ++i)
+    if (int rc = check_part(h, parts[i])) return rc;
+  // OrganizeGradients splits every partition before anything is sent (IPLS.java:1030)
+  std::vector<int64_t> nc(h->P, 0);
+  if (flat)
+    for (int p = 0; p < h->P; ++p)
+      if (int rc = split_bounds(h, p, n, &nc[p])) return rc;
+  HIP_TRY(h, dev_use(h->device));
+  if (out_kind == IPLS_DEV_TEXT && !kernel_writable(out))
+    return fail(h, IPLS_E_INVAL, "DEV_TEXT output is neither device memory nor pinned host memory");
+  if (!flat) {
+    // "did not train in time" (IPLS.java:1306-1312): Marshall_Packet(null, ...), n = 0, the header and the origin
+    std::vector<unsigned char> frame((size_t)(14 + origin_len)), text;
+    if (origin_len) std::memcpy(frame.data() + 14, origin, (size_t)origin_len);
+    for (int i = 0; i < n_parts; ++i) {
+      frame_header(frame.data(), pid, 0, h->p_lo + parts[i], iteration);
+      text.resize((size_t)lens[i]);
+      b64url_host(frame.data(), (int64_t)frame.size(), text.data());
+      if (out_kind == IPLS_HOST_TEXT) std::memcpy((unsigned char*)out + offs[i], text.data(), text.size());
+      else if (int rc = stage_h2d(h, (unsigned char*)out + offs[i], text.data(), text.size())) return rc;
+    }
+    return IPLS_OK;
+  }
+  op::Resolved sv;
+  if (op::resolve(op::kSplit, flat, n, src_kind, 0, &sv) != op::kTake) return not_taken(h, sv.why);
+  const Fmt fmt = fmt_trainer(sv.fmt) ? sv.fmt : kFmtF64;
+  const bool be_in = sv.fmt == kFmtBE;
+  const int64_t esz = fmt_size(fmt);
+  const unsigned char* dorig = nullptr;
+  if (origin_len > 0) {
+    void* d = nullptr;
+    if (int rc = upload_table(h, origin, (size_t)origin_len, &d)) return rc;
+    dorig = (const unsigned char*)d;
+  }
+  // texts land straight in a 16-B aligned device buffer; else in the scratch buffer at the same offsets, then
+  // copied out.  A host source is staged behind them: only the bytes from the first listed partition's first
+  // value to the last one's last value cross PCIe.
+  const bool direct = out_kind == IPLS_DEV_TEXT && !((uintptr_t)out & 15);
+  int64_t span = 0;
+  for (int i = 0; i < n_parts; ++i) span = std::max(span, offs[i] + lens[i]);
+  int64_t lo = span;
+  for (int i = 0; i < n_parts; ++i) lo = std::min(lo, offs[i]);
+  const int64_t text_bytes = direct ? 0 : align_up(span - lo + 64, 256);
+  int64_t s_lo = INT64_MAX, s_hi = 0;   // the listed values' range in the flat vector, in elements
+  for (int i = 0; i < n_parts; ++i) {
+    const int p = parts[i];
+    if (nc[p] == 0) continue;
+    s_lo = std::min(s_lo, h->flat_off[p]);
+    s_hi = std::max(s_hi, h->flat_off[p] + nc[p]);
+  }
+  if (s_hi == 0) s_lo = 0;
+  const int64_t src_bytes = sv.host ? (s_hi - s_lo) * esz : 0;
+  if (text_bytes + src_bytes > 0)
+    if (int rc = ensure_scratch(h, (size_t)(text_bytes + src_bytes))) return rc;
+  unsigned char* base = direct ? (unsigned char*)out : (unsigned char*)h->d_scratch - lo;
+  const char* d = (const char*)flat;   // device memory is read in place
+  int64_t d_first = 0;                 // the flat offset of d's first element
+  if (sv.host) {
+    d = (const char*)h->d_scratch + text_bytes;
+    d_first = s_lo;
+    if (int rc = stage_h2d(h, (void*)d, (const char*)flat + esz * s_lo, (size_t)src_bytes)) return rc;
+  }
+  std::vector<FlatEncJob> jobs((size_t)n_parts);
+  int64_t max_groups = 1;
+  bool any_fast = false;
+  for (int i = 0; i < n_parts; ++i) {
+    const int p = parts[i];
+    FlatEncJob& j = jobs[(size_t)i];
+    j = FlatEncJob{};
+    const int64_t L = h->len[p];
+    frame_header(j.hdr, pid, L, h->p_lo + p, iteration);
+    j.L = L;
+    j.ncopy = nc[p];
+    j.lo = nc[p] ? h->flat_off[p] - d_first : 0;
+    j.origin_len = origin_len;
+    j.origin = dorig;
+    j.out = base + offs[i];
+    j.groups = (14 + 8 * L + origin_len + 23) / 24;
+    j.text_len = lens[i];
+    max_groups = std::max(max_groups, j.groups);
+    any_fast = any_fast || nc[p] >= 5;   // lane 1's values 1 .. 4 lie below ncopy
+  }
+  void* djobs = nullptr;
+  if (int rc = upload_table(h, jobs.data(), jobs.size() * sizeof(FlatEncJob), &djobs)) return rc;
+  const unsigned gx = std::max(1u, std::min<unsigned>(blocks_for(max_groups, kBlock), 16384));
+  const dim3 grid(gx, (unsigned)n_parts);
+  if (fmt_trainer(fmt))
+    with_narrow(fmt, [&](auto s) {
+      typedef decltype(s) S;
+      hipLaunchKernelGGL((k_b64url_encode_flat<S, false>), grid, dim3(kBlock), 0, h->stream, (const FlatEncJob*)djobs,
+                         (const typename S::elem*)d);
+    });
+  else
+    with_bool(be_in, [&](auto bi) {
+      hipLaunchKernelGGL((k_b64url_encode_flat<FmtD64, decltype(bi)::value>), grid, dim3(kBlock), 0, h->stream,
+                         (const FlatEncJob*)djobs, (const unsigned long long*)d);
+    });
+  HIP_TRY(h, hipGetLastError());
+  h->last_launch = launch_info(IPLS_KERNEL_ENCODE_FLAT, 0, kBlock, 4, any_fast ? 1 : 0, 0, (int64_t)gx * n_parts, be_in,
+                               false, 0);
+  if (direct) return IPLS_OK;                           // stream-ordered
+  const hipMemcpyKind kind = out_kind == IPLS_DEV_TEXT ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  for (int i = 0; i < n_parts; ++i)
+    HIP_TRY(h, hipMemcpyAsync((unsigned char*)out + offs[i], base + offs[i], (size_t)lens[i], kind, h->stream));
+  if (out_kind == IPLS_HOST_TEXT) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return IPLS_OK;
+}
+
 // ---- saved-model files on the device (engine.hpp) ----
 static_assert(sizeof(ser_entry::prefix) == kSerPrefixMax && kSerPrefixMax == javaser::kSavedPrefixMax, "one prefix size");
 

@@ -130,6 +130,11 @@ int64_t dev_publish_many(ipls_dev* h, int n, const int* parts, int target, int32
                          const int64_t* lens, int out_kind);
 int64_t dev_publish(ipls_dev* h, int p, int target, int32_t a, int32_t b, int16_t pid, const uint8_t* origin,
                     int32_t origin_len, void* out, int64_t out_cap, int out_kind);
+// SendGradients: the pubsub texts of partitions parts[0..n_parts) (engine indices) of the flat vector, laid out
+// by the front as for dev_publish_many.  flat == null: the n = 0 texts, encoded on the host.
+int64_t dev_send_many(ipls_dev* h, const void* flat, int64_t n, int src_kind, int n_parts, const int* parts,
+                      int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
+                      const int64_t* offs, const int64_t* lens, int out_kind);
 
 // ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
 // One run of a file that an engine packs: `prefix` (framing), then engine

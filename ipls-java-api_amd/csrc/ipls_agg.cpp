@@ -45,6 +45,7 @@
 #include "flat_plan.hpp"
 #include "java_hashmap.hpp"
 #include "javaser.hpp"
+#include "operand.hpp"
 #include "pubsub_host.hpp"
 
 namespace {
@@ -1332,6 +1333,64 @@ int64_t ipls_agg_publish_partials(ipls_agg* H, const int32_t* parts, int n_parts
     H->last_shard = s;
     if (int64_t rc = dev_publish_many(H->sh[s], (int)lp.size(), lp.data(), target, a, bb.data(), pid, origin,
                                       origin_len, out, oo.data(), ll.data(), out_kind);
+        rc < 0)
+      return fwd(H, s, (int)rc);
+  }
+  return total;
+}
+
+int64_t ipls_agg_send_gradients(ipls_agg* H, const void* flat, int64_t n, int src_kind, const int32_t* parts,
+                                int n_parts, int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len,
+                                void* out, int64_t out_cap, int out_kind, int64_t* lens, int64_t* offs) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (n_parts < 0 || (n_parts > 0 && !parts)) return ferr(H, IPLS_E_INVAL, "bad partition list");
+  if (origin_len < 0 || (out && origin_len > 0 && !origin)) return ferr(H, IPLS_E_INVAL, "bad origin");
+  if (out_kind != IPLS_HOST_TEXT && out_kind != IPLS_DEV_TEXT) return ferr(H, IPLS_E_INVAL, "out_kind HOST_TEXT/DEV_TEXT");
+  std::vector<int64_t> L(n_parts), O(n_parts);
+  int64_t total = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    if (!part_ok(H, parts[i])) return range_err(H, parts[i]);
+    O[i] = (total + 63) / 64 * 64;                        // every text 64-B aligned
+    L[i] = ipls::pubsub::b64_enc_len(14 + (flat ? 8 * H->len[parts[i]] : 0) + origin_len);
+    total = O[i] + L[i];
+  }
+  if (lens) std::copy(L.begin(), L.end(), lens);
+  if (offs) std::copy(O.begin(), O.end(), offs);
+  if (!out || n_parts == 0) return total;
+  // OrganizeGradients splits EVERY partition of the model before anything is sent (IPLS.java:1030): a length
+  // error leaves the output untouched on every shard
+  if (flat)
+    for (int p = 0; p < H->P; ++p) {
+      const int64_t nc = std::max<int64_t>(0, std::min(H->off[p] + H->chunk, n) - H->off[p]);
+      if (nc > H->len[p] - 1)
+        return ferr(H, IPLS_E_RANGE, "gradient vector of %lld values overruns partition %d "
+                    "(ArrayIndexOutOfBounds, IPLS.java:1030)", (long long)n, p);
+    }
+  if (out_cap < total) return ferr(H, IPLS_E_RANGE, "gradient texts need %lld bytes", (long long)total);
+  // group by owner shard; each shard encodes its texts in one launch
+  std::vector<std::vector<int>> idx(H->S());
+  for (int i = 0; i < n_parts; ++i) idx[H->owner[parts[i]]].push_back(i);
+  const bool dev_src = flat && (ipls::operand::kDev & ipls::operand::bit(src_kind));
+  for (int s = 0; s < H->S(); ++s) {
+    if (idx[s].empty()) continue;
+    if (out_kind == IPLS_DEV_TEXT)   // the texts are written by shard s's device ...
+      if (int rc = check_reach(H, s, out, "text buffer")) return rc;
+    if (dev_src)                     // ... which reads the vector where it lies
+      if (int rc = check_reach(H, s, flat, "gradient vector")) return rc;
+  }
+  for (int s = 0; s < H->S(); ++s) {
+    if (idx[s].empty()) continue;
+    std::vector<int> lp;
+    std::vector<int64_t> oo, ll;
+    for (int i : idx[s]) {
+      lp.push_back(parts[i] - H->lo[s]);
+      oo.push_back(O[i]);
+      ll.push_back(L[i]);
+    }
+    H->last_shard = s;
+    if (int64_t rc = dev_send_many(H->sh[s], flat, n, src_kind, (int)lp.size(), lp.data(), iteration, pid, origin,
+                                   origin_len, out, oo.data(), ll.data(), out_kind);
         rc < 0)
       return fwd(H, s, (int)rc);
   }

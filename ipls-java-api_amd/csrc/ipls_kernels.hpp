@@ -1056,15 +1056,70 @@ __device__ __forceinline__ unsigned b64url_quad_lut(const unsigned char* tab, un
          ((unsigned)tab[v & 63] << 24);
 }
 
+// The three pieces below are shared with k_b64url_encode_flat, whose payload
+// is not an accumulator.
+// A fast lane's 32 chars from the 4 payload doubles its window spans, as the
+// numbers their big-endian bytes spell (v0 first): the window starts 2 bytes
+// into v0.
+__device__ __forceinline__ void window_chars(unsigned long long v0, unsigned long long v1, unsigned long long v2,
+                                             unsigned long long v3, const unsigned char* tab, u4w& c0, u4w& c1) {
+  // big-endian words of the 32 payload bytes, then the window's 6 (2 bytes in)
+  const unsigned W[8] = {(unsigned)(v0 >> 32), (unsigned)v0, (unsigned)(v1 >> 32), (unsigned)v1,
+                         (unsigned)(v2 >> 32), (unsigned)v2, (unsigned)(v3 >> 32), (unsigned)v3};
+  unsigned O[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) O[k] = (W[k] << 16) | (W[k + 1] >> 16);
+  const unsigned long long X0 = ((unsigned long long)O[0] << 32) | O[1];
+  const unsigned long long X1 = ((unsigned long long)O[2] << 32) | O[3];
+  const unsigned long long X2 = ((unsigned long long)O[4] << 32) | O[5];
+  c0.x = b64url_quad_lut(tab, (unsigned)(X0 >> 40) & 0xFFFFFF);
+  c0.y = b64url_quad_lut(tab, (unsigned)(X0 >> 16) & 0xFFFFFF);
+  c0.z = b64url_quad_lut(tab, (unsigned)((X0 << 8) | (X1 >> 56)) & 0xFFFFFF);
+  c0.w = b64url_quad_lut(tab, (unsigned)(X1 >> 32) & 0xFFFFFF);
+  c1.x = b64url_quad_lut(tab, (unsigned)(X1 >> 8) & 0xFFFFFF);
+  c1.y = b64url_quad_lut(tab, (unsigned)((X1 << 16) | (X2 >> 48)) & 0xFFFFFF);
+  c1.z = b64url_quad_lut(tab, (unsigned)(X2 >> 24) & 0xFFFFFF);
+  c1.w = b64url_quad_lut(tab, (unsigned)X2 & 0xFFFFFF);
+}
+
+// A slow lane's unit of nb = 1 .. 3 frame bytes (v = the bytes, first in bits 23:16): '=' padding on the last unit
+__device__ __forceinline__ unsigned padded_quad(unsigned v, int nb) {
+  unsigned q = b64url_quad(v);
+  if (nb < 3) q = (q & 0x00FFFFFFu) | ((unsigned)'=' << 24);
+  if (nb < 2) q = (q & 0xFF00FFFFu) | ((unsigned)'=' << 16);
+  return q;
+}
+
+// Each lane's 32 chars go through a wave-private LDS row so that every wave
+// then stores its 2 KiB of text as two contiguous 1 KiB rows (lane-strided
+// 16-B stores would leave every 128-B line half written per instruction).
+// LDS ops of one wave complete in order: a compiler barrier suffices.
+// ws = the wave's row, gw = the wave's first group.
+__device__ __forceinline__ void store_wave_text(u4w* ws, int lane, const u4w& c0, const u4w& c1,
+                                                unsigned char* __restrict__ out, int64_t gw, int64_t text_len) {
+  ws[2 * lane] = c0;
+  ws[2 * lane + 1] = c1;
+  __builtin_amdgcn_wave_barrier();
+  const int64_t wbase = 32 * gw;                  // this wave's 2 KiB of text
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const u4w v = ws[64 * h + lane];
+    const int64_t o = wbase + 1024 * h + 16 * lane;
+    if (o + 16 <= text_len) {
+      __builtin_nontemporal_store(v, (IPLS_GLOBAL u4w*)(out + o));
+    } else if (o < text_len) {   // the text's last partial 16 B
+      const unsigned w4[4] = {v.x, v.y, v.z, v.w};
+      for (int64_t c = 0; o + c < text_len; ++c) out[o + c] = (unsigned char)(w4[c >> 2] >> (8 * (c & 3)));
+    }
+  }
+  __builtin_amdgcn_wave_barrier();   // the row is rewritten by the next iteration
+}
+
 // One text: blocks [0, gridDim.x) of this job walk its groups grid-stride.
 // tab = the 64-char table in LDS, stage = 2 * kBlock 16-B rows of LDS.
 __device__ __forceinline__ void encode_frame_job(const FrameEnc& f, const unsigned long long* __restrict__ src,
                                                  unsigned char* __restrict__ out, int64_t groups, int64_t text_len,
                                                  const unsigned char* tab, u4w* stage) {
-  // Each lane's 32 chars go through a wave-private LDS row so that every wave
-  // then stores its 2 KiB of text as two contiguous 1 KiB rows (lane-strided
-  // 16-B stores would leave every 128-B line half written per instruction).
-  // LDS ops of one wave complete in order: a compiler barrier suffices.
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   u4w* ws = stage + 128 * wv;
   const int64_t F = 14 + 8 * f.n + f.origin_len;   // frame bytes
@@ -1076,23 +1131,7 @@ __device__ __forceinline__ void encode_frame_job(const FrameEnc& f, const unsign
     if (g < groups && g >= 1 && b0 + 24 <= 14 + 8 * f.n && src) {
       const unsigned long long* s = src + (3 * g - 2);
       const unsigned long long v0 = ld8(s), v1 = ld8(s + 1), v2 = ld8(s + 2), v3 = ld8(s + 3);
-      // big-endian words of the 32 payload bytes, then the window's 6 (2 bytes in)
-      const unsigned W[8] = {(unsigned)(v0 >> 32), (unsigned)v0, (unsigned)(v1 >> 32), (unsigned)v1,
-                             (unsigned)(v2 >> 32), (unsigned)v2, (unsigned)(v3 >> 32), (unsigned)v3};
-      unsigned O[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) O[k] = (W[k] << 16) | (W[k + 1] >> 16);
-      const unsigned long long X0 = ((unsigned long long)O[0] << 32) | O[1];
-      const unsigned long long X1 = ((unsigned long long)O[2] << 32) | O[3];
-      const unsigned long long X2 = ((unsigned long long)O[4] << 32) | O[5];
-      c0.x = b64url_quad_lut(tab, (unsigned)(X0 >> 40) & 0xFFFFFF);
-      c0.y = b64url_quad_lut(tab, (unsigned)(X0 >> 16) & 0xFFFFFF);
-      c0.z = b64url_quad_lut(tab, (unsigned)((X0 << 8) | (X1 >> 56)) & 0xFFFFFF);
-      c0.w = b64url_quad_lut(tab, (unsigned)(X1 >> 32) & 0xFFFFFF);
-      c1.x = b64url_quad_lut(tab, (unsigned)(X1 >> 8) & 0xFFFFFF);
-      c1.y = b64url_quad_lut(tab, (unsigned)((X1 << 16) | (X2 >> 48)) & 0xFFFFFF);
-      c1.z = b64url_quad_lut(tab, (unsigned)(X2 >> 24) & 0xFFFFFF);
-      c1.w = b64url_quad_lut(tab, (unsigned)X2 & 0xFFFFFF);
+      window_chars(v0, v1, v2, v3, tab, c0, c1);
     } else if (g < groups) {
       // header / tail lanes: byte by byte, '=' padding on the last unit
       unsigned q8[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -1103,30 +1142,12 @@ __device__ __forceinline__ void encode_frame_job(const FrameEnc& f, const unsign
         unsigned v = frame_byte(f, src, j) << 16;
         if (nb > 1) v |= frame_byte(f, src, j + 1) << 8;
         if (nb > 2) v |= frame_byte(f, src, j + 2);
-        unsigned q = b64url_quad(v);
-        if (nb < 3) q = (q & 0x00FFFFFFu) | ((unsigned)'=' << 24);
-        if (nb < 2) q = (q & 0xFF00FFFFu) | ((unsigned)'=' << 16);
-        q8[u] = q;
+        q8[u] = padded_quad(v, nb);
       }
       c0 = u4w{q8[0], q8[1], q8[2], q8[3]};
       c1 = u4w{q8[4], q8[5], q8[6], q8[7]};
     }
-    ws[2 * lane] = c0;
-    ws[2 * lane + 1] = c1;
-    __builtin_amdgcn_wave_barrier();
-    const int64_t wbase = 32 * gw;                  // this wave's 2 KiB of text
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const u4w v = ws[64 * h + lane];
-      const int64_t o = wbase + 1024 * h + 16 * lane;
-      if (o + 16 <= text_len) {
-        __builtin_nontemporal_store(v, (IPLS_GLOBAL u4w*)(out + o));
-      } else if (o < text_len) {   // the text's last partial 16 B
-        const unsigned w4[4] = {v.x, v.y, v.z, v.w};
-        for (int64_t c = 0; o + c < text_len; ++c) out[o + c] = (unsigned char)(w4[c >> 2] >> (8 * (c & 3)));
-      }
-    }
-    __builtin_amdgcn_wave_barrier();   // the row is rewritten by the next iteration
+    store_wave_text(ws, lane, c0, c1, out, gw, text_len);
   }
 }
 
@@ -2545,6 +2566,98 @@ __global__ __launch_bounds__(kBlock) void k_update_flat(const FlatJob* __restric
     }
     const double a = zero ? 0.0 : __builtin_bit_cast(double, ld8(dst + i));
     st8(dst + i, __builtin_bit_cast(unsigned long long, a + v));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// k_b64url_encode_flat: SendGradients (IPLS.java:1350-1400) -- the pubsub
+// texts of a flat gradient's partitions, one launch over a shard's listed
+// partitions (blockIdx.y = job, as in k_b64url_encode_frames).  Text =
+// Base64.getUrlEncoder(Marshall_Packet(OrganizeGradients(flat)[p], ...)), the
+// frame [14 header bytes][L x f64 BE][origin], whose payload value i is
+//   (double)src[lo + i]  i < ncopy   widened as the F32 / F16 / BF16 kinds
+//                                    are (doubles pass bit for bit; BE_IN
+//                                    byte-swaps in registers)
+//   1.0                  i == ncopy  the count slot, generated here
+//                                    (IPLS.java:1033)
+//   +0.0                 ncopy < i < L   a gradient shorter than the model
+// Nothing is added to anything: putDouble writes raw bits, so a -0.0 value is
+// -0.0 in the text.  The decomposition is k_b64url_encode_frame's: lane g owns
+// frame bytes [24g, 24g + 24); it is fast when g >= 1 and its four values
+// 3g-2 .. 3g+1 all lie below ncopy, and then loads its four source elements
+// at lo + 3g - 2 one by one (the source is only element-aligned: lo has any
+// residue) and goes through window_chars; every other lane (the header, the
+// window that holds ncopy, the zero tail, the origin) goes byte by byte.
+// ---------------------------------------------------------------------------
+struct FlatEncJob {
+  unsigned char hdr[16];          // 14 header bytes
+  int64_t L;                      // doubles in the payload
+  int64_t ncopy;                  // of which copied from the source
+  int64_t lo;                     // the partition's first element, from `src`
+  int64_t origin_len;
+  const unsigned char* origin;    // device copy of the origin bytes
+  unsigned char* out;
+  int64_t groups;
+  int64_t text_len;
+};
+
+// Payload value `p[0]` as the number its big-endian bytes spell.
+template <class S, bool BE_IN>
+__device__ __forceinline__ unsigned long long flat_value_bits(const typename S::elem* p) {
+  if constexpr (sizeof(typename S::elem) == 8) {
+    const unsigned long long v = ld8(p);
+    return BE_IN ? __builtin_bswap64(v) : v;
+  } else {
+    return __builtin_bit_cast(unsigned long long, S::widen(S::ldraw(p)));
+  }
+}
+
+template <class S, bool BE_IN>
+__global__ __launch_bounds__(kBlock) void k_b64url_encode_flat(const FlatEncJob* __restrict__ jobs,
+                                                               const typename S::elem* __restrict__ src0) {
+  typedef typename S::elem T;
+  static_assert(sizeof(T) == 8 || !BE_IN, "only doubles come big-endian");
+  __shared__ u4w stage[2 * kBlock];
+  __shared__ unsigned char tab[64];
+  init_b64url_table(tab);
+  const FlatEncJob& j = jobs[blockIdx.y];
+  const T* src = src0 + j.lo;
+  const int64_t L = j.L, ncopy = j.ncopy, groups = j.groups;
+  const int64_t F = 14 + 8 * L + j.origin_len;   // frame bytes
+  auto frame_byte_at = [&](int64_t b) -> unsigned {
+    if (b < 14) return j.hdr[b];
+    const int64_t q = b - 14;
+    if (q >= 8 * L) return j.origin[q - 8 * L];
+    const int64_t i = q >> 3;
+    const unsigned long long v = i < ncopy ? flat_value_bits<S, BE_IN>(src + i) : i == ncopy ? 0x3FF0000000000000ull : 0ull;
+    return (unsigned)(v >> (8 * (7 - (q & 7)))) & 0xFF;   // putDouble: big-endian
+  };
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  u4w* ws = stage + 128 * wv;
+  for (int64_t g0 = (int64_t)blockIdx.x * kBlock; g0 < groups; g0 += (int64_t)gridDim.x * kBlock) {
+    const int64_t gw = g0 + 64 * wv;                // this wave's first group
+    const int64_t g = gw + lane;
+    u4w c0 = {0u, 0u, 0u, 0u}, c1 = {0u, 0u, 0u, 0u};
+    if (g < groups && g >= 1 && 3 * g + 2 <= ncopy) {
+      const T* s = src + (3 * g - 2);
+      const unsigned long long v0 = flat_value_bits<S, BE_IN>(s), v1 = flat_value_bits<S, BE_IN>(s + 1);
+      const unsigned long long v2 = flat_value_bits<S, BE_IN>(s + 2), v3 = flat_value_bits<S, BE_IN>(s + 3);
+      window_chars(v0, v1, v2, v3, tab, c0, c1);
+    } else if (g < groups) {
+      unsigned q8[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+      for (int u = 0; u < 8; ++u) {
+        const int64_t b = 24 * g + 3 * u;
+        if (b >= F) break;
+        const int nb = F - b >= 3 ? 3 : (int)(F - b);
+        unsigned v = frame_byte_at(b) << 16;
+        if (nb > 1) v |= frame_byte_at(b + 1) << 8;
+        if (nb > 2) v |= frame_byte_at(b + 2);
+        q8[u] = padded_quad(v, nb);
+      }
+      c0 = u4w{q8[0], q8[1], q8[2], q8[3]};
+      c1 = u4w{q8[4], q8[5], q8[6], q8[7]};
+    }
+    store_wave_text(ws, lane, c0, c1, j.out, gw, j.text_len);
   }
 }
 

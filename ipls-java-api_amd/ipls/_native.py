@@ -33,6 +33,7 @@ KERNEL_REDUCE_H16 = 6
 KERNEL_ROUND_F32, KERNEL_ROUND_H16 = 7, 8
 KERNEL_FOLD1_F32, KERNEL_FOLD1_H16 = 9, 10   # k_fold1_narrow: one trainer-format arrival
 KERNEL_UPDATE_FLAT = 11                      # k_update_flat: one whole streamed gradient (update_gradient_chunked)
+KERNEL_ENCODE_FLAT = 12                      # k_b64url_encode_flat: a flat gradient's partitions as texts (send_gradients)
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -162,6 +163,7 @@ SIGNATURES = {
     "ipls_agg_combine_partials": (_i, [_vp, _i, _i]),
     "ipls_agg_publish_partial": (_i64, [_vp, _i, _i, _i32, _i32, _i16, _vp, _i32, _vp, _i64, _i]),
     "ipls_agg_publish_partials": (_i64, [_vp, _vp, _i, _i, _i32, _vp, _i16, _vp, _i32, _vp, _i64, _i, _vp, _vp]),
+    "ipls_agg_send_gradients": (_i64, [_vp, _vp, _i64, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp, _i64, _i, _vp, _vp]),
     "ipls_agg_last_launch": (_i, [_vp, _P(LaunchInfo)]),
     # saved-model files; the host-only encoders take typed first pointers (NULL is a valid empty input)
     "ipls_saved_parse": (_i64, [_vp, _i64, _P(_i32), _P(_i64), _P(_i64), _i64]),

@@ -1032,6 +1032,49 @@ class Aggregator:
             N.HOST_TEXT, None, None))
         return [buf[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)]
 
+    def SendGradients(self, gradients, partitions, iteration: int, *, origin: bytes = b"", pid: int = 3, out=None,
+                      out_cap: int | None = None):
+        """SendGradients -> Send_Gradient_Partition (IPLS.java:1350-1400,
+        1290-1322, direct mode): text i = Base64.getUrlEncoder(Marshall_Packet(
+        OrganizeGradients(gradients)[partitions[i]], origin, partitions[i],
+        iteration, pid)), encoded on the GPU straight from the flat vector in
+        one launch per GPU.  ``gradients`` is what UpdateGradient takes (numpy
+        float64 / float32 / float16, a CPU torch tensor, a DeviceBuffer), or
+        ``None`` for the "did not train in time" texts (n = 0).  A -0.0 stays
+        -0.0 and the count slot is generated; the text is one base64 layer
+        (the pubsub transport adds the second); secure mode's Encode is the
+        caller's.  Returns the list of texts (bytes), or, when ``out`` is a
+        DeviceBuffer / device address with ``out_cap`` bytes / PinnedBuffer,
+        the (lens, offs) of the texts written there (device: stream-ordered)."""
+        parts = np.ascontiguousarray(list(partitions), dtype=np.int32)
+        o = np.frombuffer(bytes(origin), dtype=np.uint8)
+        op = o.ctypes.data if o.size else None
+        if gradients is None:
+            ptr, ng, kind, keep = None, 0, N.HOST_F64, None
+        else:
+            if getattr(gradients, "is_cuda", False):   # a GPU torch tensor: read where it lies
+                gradients = DeviceBuffer.from_tensor(gradients)
+            ptr, ng, kind, keep = _operand(gradients, f32=True)
+        n = parts.size
+        lens = np.zeros(max(1, n), dtype=np.int64)
+        offs = np.zeros(max(1, n), dtype=np.int64)
+
+        def call(dst, cap, dst_kind, le=None, of=None):
+            return self._chk(self._lib.ipls_agg_send_gradients(
+                self._h, ptr, ng, kind, parts.ctypes.data, n, iteration, pid, op, o.size, dst, cap, dst_kind, le, of))
+
+        total = call(None, 0, N.HOST_TEXT, lens.ctypes.data, offs.ctypes.data)
+        if out is not None:
+            if isinstance(out, PinnedBuffer):
+                dst, cap, dst_kind = out.ptr, out.nbytes, N.HOST_TEXT
+            else:
+                (dst, cap), dst_kind = self._device_text_out(out, out_cap, total), N.DEV_TEXT
+            call(dst, cap, dst_kind)
+            return lens[:n].tolist(), offs[:n].tolist()
+        buf = np.empty(max(1, total), dtype=np.uint8)
+        call(buf.ctypes.data, total, N.HOST_TEXT)
+        return [buf[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)]
+
     def last_launch(self) -> dict:
         """What the last fold launch ran (kernel, shape, lanes, vectors, SEQ code, map, grid)."""
         li = N.LaunchInfo()
