@@ -40,10 +40,12 @@
 #include "operand.hpp"
 #include "pubsub_host.hpp"
 #include "reduce_plan.hpp"
+#include "stage.hpp"
 
 using namespace ipls;
 using namespace ipls::reduceplan;
 namespace op = ipls::operand;
+namespace stg = ipls::stage;
 
 namespace {
 
@@ -51,47 +53,10 @@ thread_local std::string g_tls_err;
 
 constexpr int64_t kAlignElems = 32;  // 256 B
 constexpr int kRingSlots = 4;
-constexpr int kStageSlots = 3;   // pinned slots of a chunked call's ring (IPLS_STAGE_SLOTS overrides)
 
 int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
-struct PinnedSlot {
-  void* host = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool pending = false;
-};
-
 }  // namespace
-
-// The staging of one chunked call (accumulate / finalize / get_partitions
-// _chunked), owned by that call alone from acquire to release, so the
-// caller's source or sink -- a socket recv/send, a JNI array copy -- runs
-// with no engine lock held.  A pinned host ring,
-// a device buffer for the whole bucket (or snapshot) and two copy streams of its
-// own.  Stages are pooled per shard and freed only at close.
-// Invariants at release: every pinned slot whose copy may still be in flight
-// is `pending` (its event recorded after that copy); `free_pending` says a
-// kernel on the shard stream may still read `d` (recorded after it).
-struct ipls_stage {
-  // chunk k crosses PCIe on copy[k % n_copy]: with two streams the DMA setup
-  // of chunk k + 1 overlaps the transfer of chunk k (IPLS_STAGE_STREAMS=1
-  // gives one stream, the A/B of profiles/r06)
-  hipStream_t copy[2] = {};
-  int n_copy = 0;
-  // the pinned host ring: chunk k in slot k % n_slot, so the copy engine can
-  // run up to n_slot - 1 chunks ahead of a caller's slow source or sink
-  // (IPLS_STAGE_SLOTS, 2..4)
-  static constexpr int kMaxSlots = 4;
-  PinnedSlot slot[kMaxSlots];
-  int n_slot = 0;
-  void* d = nullptr;
-  size_t d_cap = 0;
-  hipEvent_t landed[2] = {};      // copy streams -> shard stream: every chunk is in `d`
-  hipEvent_t ready = nullptr;     // shard stream -> copy streams: the snapshot is in `d`
-  hipEvent_t free_ev = nullptr;   // shard stream: the fold that read `d` has run
-  bool free_pending = false;
-};
 
 struct ipls_dev {
   std::mutex mu;
@@ -123,11 +88,10 @@ struct ipls_dev {
   std::vector<unsigned char> last_table;  // cache of the last uploaded table
   int last_slot = -1;
 
-  // staging of the chunked calls: one per concurrent call, pooled (lazily,
-  // freed at close); stage_mu guards the pool only, never taken with mu held
-  // for longer than a push
-  std::mutex stage_mu;
-  std::vector<ipls_stage*> stage_all, stage_idle;
+  // staging of the chunked calls (stage.hpp): one stage per concurrent call,
+  // pooled (lazily, freed at close); the pool's mutex is never taken with mu
+  // held for longer than a push
+  stg::Pool stages;
   // staging
   void* d_scratch = nullptr;
   size_t scratch_bytes = 0;
@@ -302,112 +266,64 @@ int fail_nl(ipls_dev* h, int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY_NL(h, expr)                                                             \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      (void)hipGetLastError();                                                          \
-      return fail_nl((h), e_ == hipErrorOutOfMemory ? IPLS_E_NOMEM : IPLS_E_DEVICE,     \
-                     "%s failed: %s", #expr, hipGetErrorString(e_));                    \
-    }                                                                                   \
-  } while (0)
+// A stage step's Status (stage.hpp) as this engine's error: with the engine lock held (`locked`) or not.
+int stage_rc(ipls_dev* h, const stg::Status& s, bool locked = false) {
+  if (!s) return IPLS_OK;
+  const auto f = locked ? fail : fail_nl;
+  return s.hip == hipSuccess ? f(h, s.code, "%s", s.what) : f(h, s.code, "%s failed: %s", s.what, hipGetErrorString(s.hip));
+}
 
-// Take an idle stage of the pool (or make one) and size it: `dev_bytes` of
-// device buffer, two pinned slots of `slot_bytes`.  Called with the engine
-// lock NOT held, on the shard's device.  Regrowing frees only memory this
-// call owns, after the copies and the kernel that last used it are done.
-int stage_acquire(ipls_dev* h, size_t dev_bytes, size_t slot_bytes, ipls_stage** out) {
-  *out = nullptr;
+// The shard's device made current on the calling thread, outside the engine lock.
+int use_nl(ipls_dev* h) { return stage_rc(h, stg::hip(dev_use(h->device), "dev_use(h->device)")); }
+
+}  // namespace
+
+// The end of a chunked call's use of its stage (engine.hpp): stage.hpp's release, its give-up path after a failure.
+void dev_stage_release(ipls_dev* h, ipls_stage* st, int rc) {
+  if (!h || !st) return;
+  if (rc) (void)dev_use(h->device);
+  stg::release(h->stages, st, rc == IPLS_OK);
+}
+
+namespace {
+
+// The outbound half every chunked read starts with: a stage of the call's own (every buffer first: a failure
+// there leaves the accumulators as they were), then under the engine lock the queued arrivals, fill(st) -- which
+// queues the snapshot into st->d on the shard stream -- and the publish.
+template <class Fill>
+int stage_snapshot(ipls_dev* h, size_t dev_bytes, size_t slot_bytes, ipls_stage** out, Fill fill) {
+  if (int rc = use_nl(h)) return rc;
   ipls_stage* st = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(h->stage_mu);
-    if (!h->stage_idle.empty()) {
-      st = h->stage_idle.back();
-      h->stage_idle.pop_back();
-    } else {
-      st = new ipls_stage();
-      h->stage_all.push_back(st);
-    }
-  }
-  auto give_back = [&](int rc) {
-    std::lock_guard<std::mutex> lk(h->stage_mu);
-    h->stage_idle.push_back(st);
-    return rc;
-  };
-  auto try_hip = [&](hipError_t e, const char* what) -> int {
-    if (e == hipSuccess) return IPLS_OK;
-    (void)hipGetLastError();
-    return fail_nl(h, e == hipErrorOutOfMemory ? IPLS_E_NOMEM : IPLS_E_DEVICE, "%s failed: %s", what,
-                   hipGetErrorString(e));
-  };
+  if (int rc = stage_rc(h, stg::acquire(h->stages, dev_bytes, slot_bytes, &st))) return rc;
   int rc = IPLS_OK;
-  if (!st->n_copy) {
-    const char* e = std::getenv("IPLS_STAGE_STREAMS");
-    st->n_copy = (e && std::atoi(e) == 1) ? 1 : 2;
-    const char* sl = std::getenv("IPLS_STAGE_SLOTS");
-    st->n_slot = sl ? std::max(2, std::min(ipls_stage::kMaxSlots, std::atoi(sl))) : kStageSlots;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    rc = flush_pending(h);
+    if (!rc) rc = fill(st);
+    if (!rc) rc = stage_rc(h, stg::publish(st, h->stream), true);
   }
-  for (int i = 0; i < st->n_copy && !rc; ++i)
-    if (!st->copy[i]) rc = try_hip(hipStreamCreateWithFlags(&st->copy[i], hipStreamNonBlocking), "hipStreamCreate");
-  for (hipEvent_t* e : {&st->landed[0], &st->landed[1], &st->ready, &st->free_ev})
-    if (!rc && !*e) rc = try_hip(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreate");
-  if (!rc && st->d_cap < dev_bytes) {
-    if (st->d) {
-      // the fold that last read `d` and every copy of the stage are done before it is freed
-      if (st->free_pending) rc = try_hip(hipEventSynchronize(st->free_ev), "hipEventSynchronize");
-      for (int i = 0; i < st->n_copy && !rc; ++i) rc = try_hip(hipStreamSynchronize(st->copy[i]), "hipStreamSynchronize");
-      if (!rc) rc = try_hip(hipFree(st->d), "hipFree");
-      if (!rc) {
-        st->d = nullptr;
-        st->d_cap = 0;
-        st->free_pending = false;
-      }
-    }
-    const size_t cap = (size_t)align_up((int64_t)dev_bytes, 1 << 20);
-    if (!rc) rc = try_hip(hipMalloc(&st->d, cap), "hipMalloc");
-    if (!rc) st->d_cap = cap;
+  if (rc) {   // a kernel of this call may have been queued before the failure
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipGetLastError();
+    dev_stage_release(h, st, rc);
+    return rc;
   }
-  for (int i = 0; i < st->n_slot; ++i) {
-    PinnedSlot& s = st->slot[i];
-    if (rc) break;
-    if (s.cap < slot_bytes) {
-      if (s.pending) rc = try_hip(hipEventSynchronize(s.ev), "hipEventSynchronize");
-      if (!rc) s.pending = false;
-      // never free a slot a copy may still read or write (the r05/h fault
-      // analysis): its last copy's event must have completed
-      if (!rc && s.host && s.ev && hipEventQuery(s.ev) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail_nl(h, IPLS_E_DEVICE, "internal: pinned slot regrown with a copy in flight");
-      }
-      if (!rc && s.host) rc = try_hip(hipHostFree(s.host), "hipHostFree");
-      if (!rc) {
-        s.host = nullptr;
-        s.cap = 0;
-        const size_t cap = std::max<size_t>(slot_bytes, 64 << 10);
-        rc = try_hip(hipHostMalloc(&s.host, cap, hipHostMallocDefault), "hipHostMalloc");
-        if (!rc) s.cap = cap;
-      }
-    }
-    if (!rc && !s.ev) rc = try_hip(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming), "hipEventCreate");
-  }
-  if (rc) return give_back(rc);
   *out = st;
   return IPLS_OK;
 }
 
-void stage_release(ipls_dev* h, ipls_stage* st) {
-  if (!st) return;
-  std::lock_guard<std::mutex> lk(h->stage_mu);
-  h->stage_idle.push_back(st);
+// The geometry checks of the chunked entries, fixed at open and so made without the lock (a target's offset is
+// not read: promote_future swaps AGG/FUT storage under it).
+int check_chunk(ipls_dev* h, int64_t chunk, const char* unit) {
+  const bool ok = chunk >= 2 && !(chunk & 1);
+  return ok ? IPLS_OK : fail_nl(h, IPLS_E_INVAL, "chunk of %lld %s: even and >= 2", (long long)chunk, unit);
 }
-
-// The host may write this pinned slot again: the copy that last read it is done.
-int stage_slot_free(ipls_dev* h, PinnedSlot& sl) {
-  if (sl.pending) {
-    HIP_TRY_NL(h, hipEventSynchronize(sl.ev));
-    sl.pending = false;
-  }
-  return IPLS_OK;
+int check_part_nl(ipls_dev* h, int p) {
+  return p >= 0 && p < h->P ? IPLS_OK : fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", p, h->P);
+}
+int check_target_nl(ipls_dev* h, int target) {
+  const bool ok = target >= IPLS_TGT_AGG && target <= IPLS_TGT_FUTURE;
+  return ok ? IPLS_OK : fail_nl(h, IPLS_E_INVAL, "bad target %d", target);
 }
 
 int ensure_scratch(ipls_dev* h, size_t bytes) {
@@ -516,7 +432,7 @@ int copy_pageable(ipls_dev* h, void* dst, const void* src, size_t bytes) {
 }
 
 // Stage one pageable per-arrival bucket into the next of the two staging
-// slots; release_stage() marks the slot busy until the fold queued after it.
+// slots; bucket_slot_busy() marks the slot busy until the fold queued after it.
 int stage_bucket(ipls_dev* h, const void* src, size_t bytes, const void** dptr) {
   ipls_dev::StageSlot& sl = h->stage[h->stage_next];
   if (sl.pending) {   // the fold that read this slot two arrivals ago
@@ -537,7 +453,7 @@ int stage_bucket(ipls_dev* h, const void* src, size_t bytes, const void** dptr) 
   return IPLS_OK;
 }
 
-int release_stage(ipls_dev* h) {
+int bucket_slot_busy(ipls_dev* h) {
   ipls_dev::StageSlot& sl = h->stage[h->stage_next];
   HIP_TRY(h, hipEventRecord(sl.free_ev, h->stream));
   sl.pending = true;
@@ -1084,21 +1000,7 @@ int dev_close(ipls_dev* h) {
     if (s.host) hipHostFree(s.host);
     if (s.ev) hipEventDestroy(s.ev);
   }
-  for (ipls_stage* st : h->stage_all) {
-    for (hipStream_t cs : st->copy)
-      if (cs) {
-        hipStreamSynchronize(cs);
-        hipStreamDestroy(cs);
-      }
-    for (auto& s : st->slot) {
-      if (s.host) hipHostFree(s.host);
-      if (s.ev) hipEventDestroy(s.ev);
-    }
-    if (st->d) hipFree(st->d);
-    for (hipEvent_t e : {st->landed[0], st->landed[1], st->ready, st->free_ev})
-      if (e) hipEventDestroy(e);
-    delete st;
-  }
+  stg::destroy(h->stages);
   if (h->copy_ev) hipEventDestroy(h->copy_ev);
   for (hipStream_t cs : h->copy_stream)
     if (cs) {
@@ -1302,7 +1204,7 @@ int dev_accumulate(ipls_dev* h, int p, int target, const void* src, int64_t n, i
   if (int rc = reduce_dev(h, p, 1, bl, 1, v.fmt, IPLS_START_ACCUM, target, nullptr, false, nullptr, false, nullptr,
                           /*arrival=*/true))
     return rc;
-  return v.host ? release_stage(h) : IPLS_OK;
+  return v.host ? bucket_slot_busy(h) : IPLS_OK;
 }
 
 int dev_accumulate_async(ipls_dev* h, int p, int target, const void* src, int64_t n, int src_kind,
@@ -1400,15 +1302,14 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
 
 // One arrival produced by the caller chunk by chunk, as one call (Updater's
 // whole-bucket fold under PeerData.mtx, Updater.java:72-149, 115-117).
-// Chunk k is filled by source() into pinned slot k % 2 of a staging of this
-// call's own and sent to its device buffer on the stage's copy stream while
-// the source fills chunk k + 1 -- all with NO engine lock held, so a source
-// that blocks (a socket recv) stalls only this call.  Once every chunk has
-// landed, the lock is taken for the fold alone: the shard stream waits for
-// the copies (an event, no host wait) and folds the whole bucket in one launch
-// (24 B per element).  So the arrival takes effect, as one unit, when its last
-// chunk has landed -- the reference's order: Middleware's Deserialize reads
-// the whole stream before UpdateModel takes PeerData.mtx (Middleware.java:224,
+// Chunk k is filled by source() into a pinned slot of a stage of this call's
+// own (stage.hpp) and sent to its device buffer while the source fills chunk
+// k + 1 -- all with NO engine lock held, so a source that blocks (a socket
+// recv) stalls only this call.  Once every chunk has landed, the lock is
+// taken for the fold alone: one launch over the whole bucket (24 B per
+// element).  So the arrival takes effect, as one unit, when its last chunk
+// has landed -- the reference's order: Middleware's Deserialize reads the
+// whole stream before UpdateModel takes PeerData.mtx (Middleware.java:224,
 // 246).  A source that stops leaves the target untouched.
 // The element format is a parameter: kFmtF64 / kFmtBE (the source
 // writes 8 B per value) or a trainer format (4 or 2 B per value, the fold is
@@ -1417,83 +1318,43 @@ int dev_accumulate_range(ipls_dev* h, int p, int target, const void* src, int64_
 static int accumulate_chunked_fmt(ipls_dev* h, int p, int target, int64_t n, int src_kind, bool narrow, int64_t chunk,
                                   ipls_chunk_source source, void* ctx) {
   if (!h || !source) return fail_nl(h, IPLS_E_INVAL, "null argument");
-  if (chunk < 2 || (chunk & 1))
-    return fail_nl(h, IPLS_E_INVAL, "chunk of %lld values: even and >= 2", (long long)chunk);
-  // geometry is fixed at open: validated without the lock (the target's
-  // offset is not read here: promote_future swaps AGG/FUT storage under it)
-  if (p < 0 || p >= h->P) return fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", p, h->P);
-  if (target < IPLS_TGT_AGG || target > IPLS_TGT_FUTURE) return fail_nl(h, IPLS_E_INVAL, "bad target %d", target);
+  if (int rc = check_chunk(h, chunk, "values")) return rc;
+  if (int rc = check_part_nl(h, p)) return rc;
+  if (int rc = check_target_nl(h, target)) return rc;
   const int64_t L = h->len[p];
   op::Resolved v;   // the kind, and a short bucket before any source call (Updater.java:115)
   if (op::resolve(narrow ? op::kChunkedNarrow : op::kChunked, nullptr, n, src_kind, L, &v) != op::kTake)
     return fail_nl(h, v.why.code, "%s", v.why.text);
   const Fmt fmt = v.fmt;
-  HIP_TRY_NL(h, dev_use(h->device));
+  if (int rc = use_nl(h)) return rc;
   const int64_t c = std::min(chunk, L);
-  const size_t esz = (size_t)fmt_size(fmt);
+  const int64_t esz = fmt_size(fmt);
   ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)L * esz, (size_t)c * esz, &st)) return rc;
-  char* d_in = (char*)st->d;
-  int rc = IPLS_OK;
-  auto try_hip = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && !rc) {
-      (void)hipGetLastError();
-      rc = fail_nl(h, IPLS_E_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
-    }
-  };
-  // the fold that last read the device buffer runs before these copies overwrite it
-  for (int i = 0; i < st->n_copy && st->free_pending; ++i)
-    try_hip(hipStreamWaitEvent(st->copy[i], st->free_ev, 0), "hipStreamWaitEvent");
+  if (int rc = stage_rc(h, stg::acquire(h->stages, (size_t)(L * esz), (size_t)(c * esz), &st))) return rc;
+  int rc = stage_rc(h, stg::begin_in(st));
   for (int64_t k = 0, off = 0; off < L && !rc; ++k, off += c) {
-    PinnedSlot& sl = st->slot[k % st->n_slot];
-    if ((rc = stage_slot_free(h, sl))) break;   // the copy of chunk k - n_slot still reads this slot
+    void* host = nullptr;
+    if ((rc = stage_rc(h, stg::slot(st, k, &host)))) break;
     const int64_t len = std::min(c, L - off);
-    if (source(ctx, sl.host, off, len) != 0) {
+    if (source(ctx, host, off, len) != 0) {
       rc = fail_nl(h, IPLS_E_INVAL, "the chunk source stopped at offset %lld: nothing folded", (long long)off);
       break;
     }
-    hipStream_t cs = st->copy[k % st->n_copy];
-    try_hip(hipMemcpyAsync(d_in + (size_t)off * esz, sl.host, (size_t)len * esz, hipMemcpyHostToDevice, cs), "hipMemcpyAsync");
-    try_hip(hipEventRecord(sl.ev, cs), "hipEventRecord");
-    if (!rc) sl.pending = true;
+    const int64_t slot_off = 0;
+    rc = stage_rc(h, stg::push(st, k, &slot_off, &off, &len, 1, (size_t)esz));
   }
-  for (int i = 0; i < st->n_copy && !rc; ++i) try_hip(hipEventRecord(st->landed[i], st->copy[i]), "hipEventRecord");
-  if (rc) {
-    // nothing folded; the copies already queued finish before the stage is reused
-    for (int i = 0; i < st->n_copy; ++i) (void)hipStreamSynchronize(st->copy[i]);
-    (void)hipGetLastError();
-    for (auto& sl : st->slot) sl.pending = false;
-    stage_release(h, st);
-    return rc;
-  }
-  {
+  if (!rc) rc = stage_rc(h, stg::landed(st));
+  if (!rc) {
     std::lock_guard<std::mutex> lk(h->mu);
     rc = flush_pending(h);   // earlier queued device buckets fold first
-    for (int i = 0; i < st->n_copy && !rc; ++i) {
-      const hipError_t e = hipStreamWaitEvent(h->stream, st->landed[i], 0);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(h, IPLS_E_DEVICE, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-      }
-    }
-    const void* bl[1] = {d_in};
+    if (!rc) rc = stage_rc(h, stg::join(st, h->stream), true);
+    const void* bl[1] = {st->d};
     if (!rc)
       rc = reduce_dev(h, p, 1, bl, 1, fmt, IPLS_START_ACCUM, target, nullptr, false, nullptr, false, nullptr,
                       /*arrival=*/true);
-    // whatever ran, nothing queued on the shard stream after this point reads `d`
-    if (hipEventRecord(st->free_ev, h->stream) == hipSuccess) {
-      st->free_pending = true;
-    } else {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(h->stream);
-      st->free_pending = false;
-    }
+    stg::mark_read(st, h->stream);
   }
-  if (rc) {   // the shard stream may not have waited for the copies: drain them
-    for (int i = 0; i < st->n_copy; ++i) (void)hipStreamSynchronize(st->copy[i]);
-    (void)hipGetLastError();
-  }
-  stage_release(h, st);
+  dev_stage_release(h, st, rc);   // after a failure nothing, or not all, was folded: the copies are drained
   return rc;
 }
 
@@ -1510,76 +1371,39 @@ int dev_accumulate_chunked_narrow(ipls_dev* h, int p, int target, int64_t n, int
 }
 
 // ---- the whole-gradient streamed update (ipls_agg_update_gradient_chunked) ----
-// The front (ipls_agg.cpp) plans the call (flat_plan.hpp) and drives one stage
-// per involved shard through these: begin, then per received chunk slot / copy,
-// then landed; every stage of the call is committed by ONE dev_flat_commit, or
-// given up by dev_flat_abort.  Nothing here but the commit takes an engine lock.
+// The front (ipls_agg.cpp) plans the call (flat_plan.hpp) and drives one stage per involved shard through these
+// (engine.hpp has the order).  Nothing here but the commit takes an engine lock.
 constexpr size_t kFlatPad = 16;   // bytes before and after the staged segment (k_update_flat's shifted loads)
 
 int dev_flat_begin(ipls_dev* h, Fmt fmt, int64_t seg, int64_t slot_elems, ipls_stage** st_out) {
   if (!h || !st_out || seg < 0 || slot_elems < 1) return fail_nl(h, IPLS_E_INVAL, "bad argument");
   *st_out = nullptr;
-  HIP_TRY_NL(h, dev_use(h->device));
+  if (int rc = use_nl(h)) return rc;
   const size_t esz = (size_t)fmt_size(fmt);
   ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)seg * esz + 2 * kFlatPad, (size_t)slot_elems * esz, &st)) return rc;
-  // the fold that last read the device buffer runs before this call's copies overwrite it
-  for (int i = 0; i < st->n_copy && st->free_pending; ++i) {
-    const hipError_t e = hipStreamWaitEvent(st->copy[i], st->free_ev, 0);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      stage_release(h, st);
-      return fail_nl(h, IPLS_E_DEVICE, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-    }
-  }
-  *st_out = st;
-  return IPLS_OK;
+  if (int rc = stage_rc(h, stg::acquire(h->stages, (size_t)seg * esz + 2 * kFlatPad, (size_t)slot_elems * esz, &st)))
+    return rc;
+  const int rc = stage_rc(h, stg::begin_in(st));
+  if (rc) dev_stage_release(h, st, rc);
+  else *st_out = st;
+  return rc;
 }
 
-// The pinned slot chunk k of this stage is received into, free to be written.
 int dev_flat_slot(ipls_dev* h, ipls_stage* st, int64_t k, void** host) {
-  HIP_TRY_NL(h, dev_use(h->device));
-  PinnedSlot& sl = st->slot[k % st->n_slot];
-  if (int rc = stage_slot_free(h, sl)) return rc;   // the copy of chunk k - n_slot still reads this slot
-  *host = sl.host;
-  return IPLS_OK;
+  if (int rc = use_nl(h)) return rc;
+  return stage_rc(h, stg::slot(st, k, host));
 }
 
-// Chunk k's H2D ranges (elements of the slot -> elements of the staged segment).
 int dev_flat_copy(ipls_dev* h, ipls_stage* st, int64_t k, Fmt fmt, const int64_t* src, const int64_t* dst,
                   const int64_t* n, int n_copies) {
   if (n_copies <= 0) return IPLS_OK;
-  HIP_TRY_NL(h, dev_use(h->device));
-  const size_t esz = (size_t)fmt_size(fmt);
-  PinnedSlot& sl = st->slot[k % st->n_slot];
-  hipStream_t cs = st->copy[k % st->n_copy];
-  char* d_in = (char*)st->d + kFlatPad;
-  for (int i = 0; i < n_copies; ++i) {
-    if (src[i] < 0 || dst[i] < 0 || n[i] < 0 || (size_t)(src[i] + n[i]) * esz > sl.cap ||
-        (size_t)(dst[i] + n[i]) * esz + 2 * kFlatPad > st->d_cap)
-      return fail_nl(h, IPLS_E_INVAL, "internal: a staged range outside its buffers");
-    HIP_TRY_NL(h, hipMemcpyAsync(d_in + (size_t)dst[i] * esz, (const char*)sl.host + (size_t)src[i] * esz,
-                                 (size_t)n[i] * esz, hipMemcpyHostToDevice, cs));
-    sl.pending = true;   // from the first queued copy on: the event below, or the abort's drain, clears it
-  }
-  HIP_TRY_NL(h, hipEventRecord(sl.ev, cs));
-  return IPLS_OK;
+  if (int rc = use_nl(h)) return rc;
+  return stage_rc(h, stg::push(st, k, src, dst, n, n_copies, (size_t)fmt_size(fmt), kFlatPad));
 }
 
 int dev_flat_landed(ipls_dev* h, ipls_stage* st) {
-  HIP_TRY_NL(h, dev_use(h->device));
-  for (int i = 0; i < st->n_copy; ++i) HIP_TRY_NL(h, hipEventRecord(st->landed[i], st->copy[i]));
-  return IPLS_OK;
-}
-
-// Give the stage up: the copies already queued finish before it is reused.
-void dev_flat_abort(ipls_dev* h, ipls_stage* st) {
-  if (!h || !st) return;
-  (void)dev_use(h->device);
-  for (int i = 0; i < st->n_copy; ++i) (void)hipStreamSynchronize(st->copy[i]);
-  (void)hipGetLastError();
-  for (auto& sl : st->slot) sl.pending = false;
-  stage_release(h, st);
+  if (int rc = use_nl(h)) return rc;
+  return stage_rc(h, stg::landed(st));
 }
 
 template <class S, bool BE>
@@ -1599,20 +1423,9 @@ int dev_flat_commit(const flat_commit* c, int n, Fmt fmt) {
   for (int s = 0; s < n; ++s) c[s].h->mu.lock();
   for (int s = 0; s < n && !rc; ++s) {
     ipls_dev* h = c[s].h;
-    const hipError_t e0 = dev_use(h->device);
-    if (e0 != hipSuccess) {
-      (void)hipGetLastError();
-      rc = fail(h, IPLS_E_DEVICE, "dev_use failed: %s", hipGetErrorString(e0));
-      break;
-    }
-    rc = flush_pending(h);   // earlier queued device buckets fold first
-    for (int i = 0; i < c[s].st->n_copy && !rc; ++i) {
-      const hipError_t e = hipStreamWaitEvent(h->stream, c[s].st->landed[i], 0);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(h, IPLS_E_DEVICE, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-      }
-    }
+    rc = stage_rc(h, stg::hip(dev_use(h->device), "dev_use"), true);
+    if (!rc) rc = flush_pending(h);   // earlier queued device buckets fold first
+    if (!rc) rc = stage_rc(h, stg::join(c[s].st, h->stream), true);
   }
   const int64_t tile = fmt_trainer(fmt) ? flat_tile<FmtF32>() : flat_tile<FmtD64>();
   for (int s = 0; s < n && !rc; ++s) {
@@ -1660,91 +1473,41 @@ int dev_flat_commit(const flat_commit* c, int n, Fmt fmt) {
     }();
   }
   for (int s = 0; s < n; ++s) {
-    ipls_dev* h = c[s].h;
-    ipls_stage* st = c[s].st;
-    // whatever ran, nothing queued on the shard stream after this point reads `d`
-    if (dev_use(h->device) == hipSuccess && hipEventRecord(st->free_ev, h->stream) == hipSuccess) {
-      st->free_pending = true;
-    } else {
-      (void)hipGetLastError();
-      (void)hipStreamSynchronize(h->stream);
-      st->free_pending = false;
-    }
+    if (dev_use(c[s].h->device) != hipSuccess) (void)hipGetLastError();   // (the record then fails: a synchronise)
+    stg::mark_read(c[s].st, c[s].h->stream);
   }
   for (int s = n - 1; s >= 0; --s) c[s].h->mu.unlock();
-  for (int s = 0; s < n; ++s) {
-    if (rc) {   // a shard stream may not have waited for the copies: drain them
-      (void)dev_use(c[s].h->device);
-      for (int i = 0; i < c[s].st->n_copy; ++i) (void)hipStreamSynchronize(c[s].st->copy[i]);
-      (void)hipGetLastError();
-      for (auto& sl : c[s].st->slot) sl.pending = false;
-    }
-    stage_release(c[s].h, c[s].st);
-  }
+  // after a failure a shard stream may not have waited for the copies: they are drained
+  for (int s = 0; s < n; ++s) dev_stage_release(c[s].h, c[s].st, rc);
   return rc;
 }
 
-// A stage's device snapshot (complete once st->ready fires) handed out in
-// pieces, with no engine lock held: piece k + 1 crosses PCIe into one pinned
-// slot on the stage's copy stream while the consumer has piece k from the
-// other.  The ring itself, in bytes: bytes [0, n) at `d` go to call(host, off,
-// len) in pieces of c bytes; a non-zero return stops it and is returned.  The
-// stage stays the caller's.
+// A stage's published snapshot handed out through its ring (stg::ring), no engine lock held.
 template <class Call>
 static int stage_ring(ipls_dev* h, ipls_stage* st, const char* d, int64_t n, int64_t c, Call call) {
-  int rc = IPLS_OK;
-  auto try_hip = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && !rc) {
-      (void)hipGetLastError();
-      rc = fail_nl(h, IPLS_E_DEVICE, "%s failed: %s", what, hipGetErrorString(e));
-    }
-  };
-  // a previous call's H2D may still read a slot (accumulate_chunked does not
-  // wait for its copies on the host): the D2H into it waits for that copy
-  for (auto& sl : st->slot)
-    if (!rc) rc = stage_slot_free(h, sl);
-  for (int i = 0; i < st->n_copy; ++i) try_hip(hipStreamWaitEvent(st->copy[i], st->ready, 0), "hipStreamWaitEvent");
-  const int64_t K = n > 0 ? (n + c - 1) / c : 0;
-  const int S = st->n_slot;
-  int64_t issued = 0;
-  auto issue = [&]() {   // the next chunk, into slot issued % S (its previous chunk's sink has returned)
-    const int64_t k = issued++;
-    PinnedSlot& sl = st->slot[k % S];
-    const int64_t off = k * c, len = std::min(c, n - off);
-    hipStream_t cs = st->copy[k % st->n_copy];
-    try_hip(hipMemcpyAsync(sl.host, d + off, (size_t)len, hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
-    try_hip(hipEventRecord(sl.ev, cs), "hipEventRecord");
-  };
-  while (issued < K && issued < S && !rc) issue();   // the ring's first fill
-  for (int64_t k = 0; k < K && !rc; ++k) {
-    PinnedSlot& sl = st->slot[k % S];
-    try_hip(hipEventSynchronize(sl.ev), "hipEventSynchronize");
-    if (rc) break;
-    const int64_t off = k * c, len = std::min(c, n - off);
-    if ((rc = call(sl.host, off, len)) != 0) break;
-    if (issued < K) issue();   // into the slot just consumed
-  }
-  // every copy of this call is done before the stage can be reused (on the
-  // success path they already are: each chunk's event was waited for)
-  if (rc) {
-    for (int i = 0; i < st->n_copy; ++i) (void)hipStreamSynchronize(st->copy[i]);
-    (void)hipGetLastError();
-  }
-  for (auto& sl : st->slot) sl.pending = false;
-  return rc;
+  stg::Status err;
+  const int rc = stg::ring(st, d, n, c, &err, call);
+  return err ? stage_rc(h, err) : rc;
 }
 
 // n values of the snapshot to the sink in chunks of c; `base` is added to the
-// offsets the sink sees.  Releases the stage.
+// offsets the sink sees.
 static int stage_deliver(ipls_dev* h, ipls_stage* st, int64_t n, int64_t c, int64_t base, ipls_chunk_sink sink, void* ctx,
                   const char* stopped_note) {
-  const int rc = stage_ring(h, st, (const char*)st->d, 8 * n, 8 * c, [&](const void* host, int64_t off, int64_t len) {
+  return stage_ring(h, st, (const char*)st->d, 8 * n, 8 * c, [&](const void* host, int64_t off, int64_t len) {
     if (sink(ctx, (const double*)host, base + off / 8, len / 8) == 0) return IPLS_OK;
     return fail_nl(h, IPLS_E_INVAL, "the chunk sink stopped the transfer at offset %lld%s", (long long)(base + off / 8),
                    stopped_note);
   });
-  stage_release(h, st);
-  return rc;
+}
+
+// The same for a byte sink: bytes [0, n) at d, seen by the sink at offsets base, base + 1, ...
+static int stage_deliver_bytes(ipls_dev* h, ipls_stage* st, const char* d, int64_t n, int64_t c, int64_t base,
+                               ipls_byte_sink sink, void* ctx) {
+  return stage_ring(h, st, d, n, c, [&](const void* host, int64_t off, int64_t len) {
+    if (sink(ctx, (const uint8_t*)host, base + off, len) == 0) return IPLS_OK;
+    return fail_nl(h, IPLS_E_INVAL, "the byte sink stopped the transfer at offset %lld", (long long)(base + off));
+  });
 }
 
 // The reverse: target[off..off+n) of partition p into pinned host memory,
@@ -1814,7 +1577,7 @@ static int gbuf_load(ipls_dev* h, const void* bytes, int64_t n_bytes, bool* zero
     launch_bswap(h->stream, (const unsigned long long*)dsrc, h->d_gbuf, nw);
     HIP_TRY(h, hipGetLastError());
     if (!*zero_copy)
-      if (int rc = release_stage(h)) return rc;
+      if (int rc = bucket_slot_busy(h)) return rc;
   }
   if (nd > G) {
     if (*zero_copy) HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2082,45 +1845,30 @@ int dev_finalize(ipls_dev* h, int p, void* sum_out, int sum_kind, double* avg_ou
 // (Middleware.java:254).
 int dev_finalize_chunked(ipls_dev* h, int p, int sum_kind, int64_t chunk, ipls_chunk_sink sink, void* ctx) {
   if (!h || !sink) return fail_nl(h, IPLS_E_INVAL, "null argument");
-  if (chunk < 2 || (chunk & 1))
-    return fail_nl(h, IPLS_E_INVAL, "chunk of %lld values: even and >= 2", (long long)chunk);
-  if (p < 0 || p >= h->P) return fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", p, h->P);
+  if (int rc = check_chunk(h, chunk, "values")) return rc;
+  if (int rc = check_part_nl(h, p)) return rc;
   if (sum_kind != IPLS_HOST_F64 && sum_kind != IPLS_HOST_BE)
     return fail_nl(h, IPLS_E_INVAL, "sum_kind must be HOST_F64 or HOST_BE");
-  const int64_t L = h->len[p];
-  HIP_TRY_NL(h, dev_use(h->device));
-  const int64_t c = std::min(chunk, L);
-  // every buffer first: a failure here leaves the round in place
+  const int64_t L = h->len[p], c = std::min(chunk, L);
   ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)L * 8, (size_t)c * 8, &st)) return rc;
-  int rc = IPLS_OK;
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    rc = flush_pending(h);
-    if (!rc) rc = finalize_range(h, p, 1);
-    if (!rc) {
-      const unsigned long long* w = (const unsigned long long*)(h->arena + h->w_off[p]);
-      hipError_t e;
-      if (sum_kind == IPLS_HOST_BE) {
-        launch_bswap(h->stream, w, (unsigned long long*)st->d, L);
-        e = hipGetLastError();
-      } else {
-        e = hipMemcpyAsync(st->d, w, (size_t)L * 8, hipMemcpyDeviceToDevice, h->stream);
-      }
-      if (e == hipSuccess) e = hipEventRecord(st->ready, h->stream);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(h, IPLS_E_DEVICE, "W snapshot: %s", hipGetErrorString(e));
-      }
+  int rc = stage_snapshot(h, (size_t)L * 8, (size_t)c * 8, &st, [&](ipls_stage* s) {
+    if (int r = finalize_range(h, p, 1)) return r;
+    const unsigned long long* w = (const unsigned long long*)(h->arena + h->w_off[p]);
+    hipError_t e;
+    if (sum_kind == IPLS_HOST_BE) {
+      launch_bswap(h->stream, w, (unsigned long long*)s->d, L);
+      e = hipGetLastError();
+    } else {
+      e = hipMemcpyAsync(s->d, w, (size_t)L * 8, hipMemcpyDeviceToDevice, h->stream);
     }
-  }
-  if (rc) {   // a kernel of this call may have been queued before the failure
-    (void)hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) return IPLS_OK;
     (void)hipGetLastError();
-    stage_release(h, st);
-    return rc;
-  }
-  return stage_deliver(h, st, L, c, 0, sink, ctx, " (the round is consumed)");
+    return fail(h, IPLS_E_DEVICE, "W snapshot: %s", hipGetErrorString(e));
+  });
+  if (rc) return rc;
+  rc = stage_deliver(h, st, L, c, 0, sink, ctx, " (the round is consumed)");
+  dev_stage_release(h, st, rc);
+  return rc;
 }
 
 int dev_set_weights(ipls_dev* h, int p, const void* src, int64_t n, int src_kind) {
@@ -2504,45 +2252,21 @@ int dev_get_partitions(ipls_dev* h, void* out, int64_t n, int out_kind) {
 int dev_get_partitions_snapshot(ipls_dev* h, int64_t chunk, bool wire, ipls_stage** st_out, Fmt fmt) {
   *st_out = nullptr;
   if (!h) return fail_nl(h, IPLS_E_INVAL, "null argument");
-  if (chunk < 2 || (chunk & 1))
-    return fail_nl(h, IPLS_E_INVAL, "chunk of %lld %s: even and >= 2", (long long)chunk,
-                   fmt_trainer(fmt) ? "values" : "doubles");
+  if (int rc = check_chunk(h, chunk, fmt_trainer(fmt) ? "values" : "doubles")) return rc;
   if (wire && fmt_trainer(fmt)) return fail_nl(h, IPLS_E_INVAL, "the wire stream holds doubles");
   const int64_t M = h->flat_total - h->flat_base;
   if (M <= 0) return IPLS_OK;
-  HIP_TRY_NL(h, dev_use(h->device));
   const size_t esz = (size_t)fmt_size(fmt);
-  ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)M * esz, (size_t)std::min(chunk, M) * esz, &st)) return rc;
-  int rc = IPLS_OK;
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    rc = flush_pending(h);
-    if (!rc)
-      rc = fmt_trainer(fmt) ? divide_range_narrow(h, 0, h->P, st->d, fmt)
+  return stage_snapshot(h, (size_t)M * esz, (size_t)std::min(chunk, M) * esz, st_out, [&](ipls_stage* st) {
+    return fmt_trainer(fmt) ? divide_range_narrow(h, 0, h->P, st->d, fmt)
                             : divide_range(h, 0, h->P, (unsigned long long*)st->d, wire);
-    if (!rc) {
-      const hipError_t e = hipEventRecord(st->ready, h->stream);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(h, IPLS_E_DEVICE, "hipEventRecord failed: %s", hipGetErrorString(e));
-      }
-    }
-  }
-  if (rc) {   // a kernel of this call may have been queued before the failure
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    stage_release(h, st);
-    return rc;
-  }
-  *st_out = st;
-  return IPLS_OK;
+  });
 }
 
 int dev_get_partitions_deliver(ipls_dev* h, ipls_stage* st, int64_t chunk, ipls_chunk_sink sink, void* ctx) {
   if (!st) return IPLS_OK;
   const int64_t M = h->flat_total - h->flat_base;
-  HIP_TRY_NL(h, dev_use(h->device));
+  if (int rc = use_nl(h)) return rc;
   return stage_deliver(h, st, M, std::min(chunk, M), h->flat_base, sink, ctx, "");
 }
 
@@ -2552,32 +2276,8 @@ int dev_get_partitions_deliver_narrow(ipls_dev* h, ipls_stage* st, int64_t chunk
                                       void* ctx) {
   if (!st) return IPLS_OK;
   const int64_t M = h->flat_total - h->flat_base, esz = fmt_size(fmt);
-  HIP_TRY_NL(h, dev_use(h->device));
-  const int64_t base = h->flat_base * esz;
-  const int rc = stage_ring(h, st, (const char*)st->d, M * esz, std::min(chunk, M) * esz,
-                            [&](const void* host, int64_t off, int64_t len) {
-                              if (sink(ctx, (const uint8_t*)host, base + off, len) == 0) return IPLS_OK;
-                              return fail_nl(h, IPLS_E_INVAL, "the byte sink stopped the transfer at offset %lld",
-                                             (long long)(base + off));
-                            });
-  stage_release(h, st);
-  return rc;
-}
-
-// A snapshot that is not delivered (another shard failed first): the divide
-// that writes it finishes before the stage can be reused.
-void dev_stage_release(ipls_dev* h, ipls_stage* st) {
-  if (!st) return;
-  (void)dev_use(h->device);
-  if (hipEventSynchronize(st->ready) != hipSuccess) (void)hipGetLastError();
-  stage_release(h, st);
-}
-
-int dev_get_partitions_chunked(ipls_dev* h, int64_t chunk, ipls_chunk_sink sink, void* ctx, bool wire) {
-  if (!h || !sink) return fail_nl(h, IPLS_E_INVAL, "null argument");
-  ipls_stage* st = nullptr;
-  if (int rc = dev_get_partitions_snapshot(h, chunk, wire, &st)) return rc;
-  return dev_get_partitions_deliver(h, st, chunk, sink, ctx);
+  if (int rc = use_nl(h)) return rc;
+  return stage_deliver_bytes(h, st, (const char*)st->d, M * esz, std::min(chunk, M) * esz, h->flat_base * esz, sink, ctx);
 }
 
 // ---- device utilities ----
@@ -3534,8 +3234,8 @@ int dev_ser_pack(ipls_dev* h, const ser_entry* entries, int n, int target, bool 
   int64_t total = 0, max_words = 1;
   for (int i = 0; i < n; ++i) {
     const ser_entry& e = entries[i];
-    if (e.q < 0 || e.q >= h->P) return fail_nl(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", e.q, h->P);
-    if (target_off(h, e.q, target) < 0) return fail_nl(h, IPLS_E_INVAL, "bad target %d", target);
+    if (int rc = check_part_nl(h, e.q)) return rc;
+    if (int rc = check_target_nl(h, target)) return rc;
     if (e.prefix_len < (boxed ? 6 : 0) || e.prefix_len > kSerPrefixMax) return fail_nl(h, IPLS_E_INVAL, "bad prefix");
     SerPackJob& j = jobs[(size_t)i];
     j = SerPackJob{};
@@ -3548,53 +3248,30 @@ int dev_ser_pack(ipls_dev* h, const ser_entry* entries, int n, int target, bool 
     total += e.prefix_len + body + (e.suffix >= 0 ? 1 : 0);
     max_words = std::max(max_words, body / 16 + 1);
   }
-  HIP_TRY_NL(h, dev_use(h->device));
-  ipls_stage* st = nullptr;
-  if (int rc = stage_acquire(h, (size_t)total + 32, (size_t)std::max<int64_t>(16, std::min(slot_bytes, total)), &st))
-    return rc;
-  int rc = IPLS_OK;
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    rc = flush_pending(h);
-    for (int i = 0; i < n && !rc; ++i) {
+  *nbytes = total;
+  const size_t slot = (size_t)std::max<int64_t>(16, std::min(slot_bytes, total));
+  return stage_snapshot(h, (size_t)total + 32, slot, st_out, [&](ipls_stage* st) {
+    for (int i = 0; i < n; ++i) {
       const uint8_t* zf = zero_flag(h, entries[i].q, target);
       jobs[(size_t)i].src =
           (zf && *zf) ? nullptr : (const unsigned long long*)(h->arena + target_off(h, entries[i].q, target));
     }
     void* djobs = nullptr;
-    if (!rc) rc = upload_table(h, jobs.data(), jobs.size() * sizeof(SerPackJob), &djobs);
-    if (!rc) {
-      const dim3 grid(std::max(1u, std::min<unsigned>(blocks_for(max_words, kSerTileWords), 16384)), (unsigned)n);
-      if (boxed) hipLaunchKernelGGL(k_ser_pack_boxed, grid, dim3(kBlock), 0, h->stream, (const SerPackJob*)djobs, (unsigned char*)st->d);
-      else hipLaunchKernelGGL(k_ser_pack, grid, dim3(kBlock), 0, h->stream, (const SerPackJob*)djobs, (unsigned char*)st->d);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess) e = hipEventRecord(st->ready, h->stream);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(h, IPLS_E_DEVICE, "saved-model pack: %s", hipGetErrorString(e));
-      }
-    }
-  }
-  if (rc) {   // a kernel of this call may have been queued before the failure
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    stage_release(h, st);
-    return rc;
-  }
-  *st_out = st;
-  *nbytes = total;
-  return IPLS_OK;
+    if (int r = upload_table(h, jobs.data(), jobs.size() * sizeof(SerPackJob), &djobs)) return r;
+    const dim3 grid(std::max(1u, std::min<unsigned>(blocks_for(max_words, kSerTileWords), 16384)), (unsigned)n);
+    if (boxed) hipLaunchKernelGGL(k_ser_pack_boxed, grid, dim3(kBlock), 0, h->stream, (const SerPackJob*)djobs, (unsigned char*)st->d);
+    else hipLaunchKernelGGL(k_ser_pack, grid, dim3(kBlock), 0, h->stream, (const SerPackJob*)djobs, (unsigned char*)st->d);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? IPLS_OK : fail(h, IPLS_E_DEVICE, "saved-model pack: %s", hipGetErrorString(e));
+  });
 }
 
 int dev_ser_deliver(ipls_dev* h, ipls_stage* st, int64_t off, int64_t n, int64_t chunk, int64_t base, ipls_byte_sink sink,
                     void* ctx) {
   if (!h || !st || !sink || chunk < 16) return fail_nl(h, IPLS_E_INVAL, "bad argument");
-  HIP_TRY_NL(h, dev_use(h->device));
+  if (int rc = use_nl(h)) return rc;
   const int64_t c = std::min<int64_t>(chunk, (int64_t)st->slot[0].cap);
-  return stage_ring(h, st, (const char*)st->d + off, n, c, [&](const void* host, int64_t o, int64_t len) {
-    if (sink(ctx, (const uint8_t*)host, base + o, len) == 0) return IPLS_OK;
-    return fail_nl(h, IPLS_E_INVAL, "the byte sink stopped the transfer at offset %lld", (long long)(base + o));
-  });
+  return stage_deliver_bytes(h, st, (const char*)st->d + off, n, c, base, sink, ctx);
 }
 
 int dev_ser_apply(ipls_dev* h, const uint8_t* bytes, int64_t lo, int64_t hi, const int* q, const int64_t* offs, int n,

@@ -17,7 +17,7 @@
 #include "fmt.hpp"
 
 struct ipls_dev;
-struct ipls_stage;   // the staging one chunked call owns (engine.hip)
+struct ipls_stage;   // the staging one chunked call owns (stage.hpp)
 
 const char* dev_last_error(const ipls_dev* h);
 void dev_set_thread_error(const char* msg);
@@ -64,7 +64,8 @@ int dev_accumulate_chunked_narrow(ipls_dev* h, int p, int target, int64_t n, int
 // any of them.  dev_flat_commit then applies every stage of the call as one
 // unit (the engines' locks in the order given, all held at once; per shard
 // flush_pending, a wait for its copies, its launches of k_update_flat) and
-// releases the stages; dev_flat_abort drains and releases one instead.
+// releases the stages; a call that fails before it gives each stage back with
+// dev_stage_release and its error.
 struct flat_job {
   int q;                 // engine-local partition
   int64_t lo, ncopy;     // first element in the staged segment, values copied
@@ -81,20 +82,26 @@ int dev_flat_slot(ipls_dev* h, ipls_stage* st, int64_t k, void** host);
 int dev_flat_copy(ipls_dev* h, ipls_stage* st, int64_t k, Fmt fmt, const int64_t* src, const int64_t* dst,
                   const int64_t* n, int n_copies);
 int dev_flat_landed(ipls_dev* h, ipls_stage* st);
-void dev_flat_abort(ipls_dev* h, ipls_stage* st);
 int dev_flat_commit(const flat_commit* c, int n, Fmt fmt);
 int dev_finalize_chunked(ipls_dev* h, int p, int sum_kind, int64_t chunk, ipls_chunk_sink sink, void* ctx);
-int dev_get_partitions_chunked(ipls_dev* h, int64_t chunk, ipls_chunk_sink sink, void* ctx, bool wire);
-// the two phases of dev_get_partitions_chunked: the snapshot under the
+// the two phases of ipls_agg_get_partitions_chunked on one engine: the snapshot under the
 // engine lock (into a stage the call owns; null for an empty segment), then
-// the delivery to the sink with no lock held, which releases the stage
+// the delivery to the sink with no lock held
 // (fmt: a trainer format makes the snapshot the narrowed model, which
 // dev_get_partitions_deliver_narrow hands out as bytes)
 int dev_get_partitions_snapshot(ipls_dev* h, int64_t chunk, bool wire, ipls_stage** st, Fmt fmt = kFmtF64);
 int dev_get_partitions_deliver(ipls_dev* h, ipls_stage* st, int64_t chunk, ipls_chunk_sink sink, void* ctx);
 int dev_get_partitions_deliver_narrow(ipls_dev* h, ipls_stage* st, int64_t chunk, Fmt fmt, ipls_byte_sink sink,
                                       void* ctx);
-void dev_stage_release(ipls_dev* h, ipls_stage* st);
+// Stage ownership, one rule: a stage that dev_flat_begin, dev_get_partitions
+// _snapshot or dev_ser_pack handed out stays the caller's through every
+// dev_flat_* step and dev_*_deliver and goes back through exactly one
+// dev_stage_release with the call's result (null st: nothing to do) -- but a
+// dev_flat_commit takes its stages with it.  IPLS_OK returns the stage to the
+// pool; anything else (a source or sink that stopped, a snapshot never
+// delivered) first waits for its copies and its snapshot (the give-up path of
+// stage.hpp's release).
+void dev_stage_release(ipls_dev* h, ipls_stage* st, int rc);
 int dev_update_indirect(ipls_dev* h, int p, int target, const void* bytes, int64_t n_bytes);
 int dev_gbuf_load(ipls_dev* h, const void* bytes, int64_t n_bytes, const void** gbuf, int64_t* glen);
 int dev_other_replica(ipls_dev* h, int p, int32_t aggregator, const void* src, int64_t n, int src_kind);
@@ -152,7 +159,7 @@ struct ser_entry {
 int dev_ser_pack(ipls_dev* h, const ser_entry* entries, int n, int target, bool boxed, int64_t slot_bytes,
                  ipls_stage** st, int64_t* nbytes);
 // Image bytes [off, off + n) to the sink in pieces of at most `chunk`, as file
-// bytes base, base + 1, ...; no lock held.  Keeps the stage.
+// bytes base, base + 1, ...; no lock held.
 int dev_ser_deliver(ipls_dev* h, ipls_stage* st, int64_t off, int64_t n, int64_t chunk, int64_t base,
                     ipls_byte_sink sink, void* ctx);
 // target[q[i]] = or blended with the big-endian payload at file byte offs[i]

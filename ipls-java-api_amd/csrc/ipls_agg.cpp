@@ -712,8 +712,7 @@ int ipls_agg_update_gradient_chunked(ipls_agg* H, int64_t n, int src_kind, const
   std::vector<char> landed((size_t)NS, 0);
   auto dev = [&](int k) { return H->sh[(size_t)pl.shards[(size_t)k].shard]; };
   auto give_up = [&](int rc) {
-    for (int k = 0; k < NS; ++k)
-      if (st[(size_t)k]) dev_flat_abort(dev(k), st[(size_t)k]);
+    for (int k = 0; k < NS; ++k) dev_stage_release(dev(k), st[(size_t)k], rc);
     return rc;
   };
   int rc = IPLS_OK;
@@ -1166,13 +1165,9 @@ int get_partitions_chunked(ipls_agg* H, int64_t chunk, ipls_chunk_sink sink, voi
   int rc = IPLS_OK;
   size_t i = 0;
   for (; i < ss.size() && !rc; ++i) rc = fwd(H, ss[i], dev_get_partitions_snapshot(H->sh[ss[i]], chunk, wire, &st[i]));
-  for (size_t j = 0; j < ss.size(); ++j) {
-    if (!rc && j < i) {
-      rc = fwd(H, ss[j], dev_get_partitions_deliver(H->sh[ss[j]], st[j], chunk, sink, ctx));
-    } else if (st[j]) {
-      dev_stage_release(H->sh[ss[j]], st[j]);   // after a failure: nothing more is delivered
-    }
-  }
+  for (size_t j = 0; j < i && !rc; ++j)   // after a failure nothing more is delivered
+    rc = fwd(H, ss[j], dev_get_partitions_deliver(H->sh[ss[j]], st[j], chunk, sink, ctx));
+  for (size_t j = 0; j < i; ++j) dev_stage_release(H->sh[ss[j]], st[j], rc);
   return rc;
 }
 }  // namespace
@@ -1200,13 +1195,9 @@ int ipls_agg_get_partitions_chunked_narrow(ipls_agg* H, int out_kind, int64_t ch
   size_t i = 0;
   for (; i < ss.size() && !rc; ++i)
     rc = fwd(H, ss[i], dev_get_partitions_snapshot(H->sh[ss[i]], chunk, false, &st[i], fmt));
-  for (size_t j = 0; j < ss.size(); ++j) {
-    if (!rc && j < i) {
-      rc = fwd(H, ss[j], dev_get_partitions_deliver_narrow(H->sh[ss[j]], st[j], chunk, fmt, sink, ctx));
-    } else if (st[j]) {
-      dev_stage_release(H->sh[ss[j]], st[j]);   // after a failure: nothing more is delivered
-    }
-  }
+  for (size_t j = 0; j < i && !rc; ++j)   // after a failure nothing more is delivered
+    rc = fwd(H, ss[j], dev_get_partitions_deliver_narrow(H->sh[ss[j]], st[j], chunk, fmt, sink, ctx));
+  for (size_t j = 0; j < i; ++j) dev_stage_release(H->sh[ss[j]], st[j], rc);
   return rc;
 }
 
@@ -1478,7 +1469,7 @@ int save_stream(ipls_agg* H, const std::vector<ser_entry>& ents, bool boxed, int
     rc = fwd(H, g.s, dev_ser_deliver(H->sh[g.s], st[g.s], g.off, g.len, chunk, g.base, sink, ctx));
   }
   for (int s = 0; s < H->S(); ++s)
-    if (st[s]) dev_stage_release(H->sh[s], st[s]);
+    dev_stage_release(H->sh[s], st[s], rc);
   return rc;
 }
 
