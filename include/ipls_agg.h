@@ -821,6 +821,53 @@ int64_t ipls_agg_send_gradients(ipls_agg *h, const void *flat, int64_t n, int sr
                                 const uint8_t *origin, int32_t origin_len,
                                 void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
 
+/* ---- the trainer boundary over a LIST of arrays (no flat copy in or out) ----
+ *
+ * A trainer's model is a list of parameter tensors, its gradient a list of
+ * separately allocated arrays, often of mixed precision.  A SEGMENT LIST is
+ * n_segs device arrays (ptrs[s], ns[s] elements, kinds[s]); kinds[s] is
+ * IPLS_DEV_F64, IPLS_DEV_F32, IPLS_DEV_F16 or IPLS_DEV_BF16, mixed freely.
+ * The flat vector it stands for is the concatenation of the segments in list
+ * order (parameters_to_vector order, each array read in memory order), of
+ * n = sum of ns[s] values; value f is (double)ptrs[s][f - start_s], widened by
+ * the rule stated above for that kind.  Everything after that is what the flat
+ * call does with that vector:
+ *   ipls_agg_update_gradient_segs  the accumulators end with the bits of
+ *       ipls_agg_update_gradient(IPLS_DEV_F64) fed the widened concatenation
+ *       (count slot 1.0 generated, +0.0 above it, the add always made);
+ *   ipls_agg_send_gradients_segs   the texts of ipls_agg_send_gradients fed
+ *       the same (a -0.0 stays -0.0, the count slot is generated);
+ *   ipls_agg_get_partitions_segs   element f of the OUTPUT list is what
+ *       ipls_agg_get_partitions writes at f for that segment's kind: doubles
+ *       as they are, F32 one rounding of the IEEE double quotient, F16 / BF16
+ *       the two-step rule; zero-count passthrough and secure mode included.
+ * The list: a zero-length segment is legal and holds nothing (its pointer is
+ * not looked at); n_segs == 0 is a vector of NO values -- not the null
+ * gradient, which keeps going through the flat calls; every pointer of a
+ * non-empty segment must be non-NULL and aligned to its element size, else
+ * IPLS_E_INVAL naming the segment; host kinds, BE kinds, unknown kinds and a
+ * negative length are IPLS_E_INVAL.  Input segments may alias each other;
+ * overlapping output segments are the caller's problem.
+ * Order of checks and effects, exactly the flat twins': every partition of the
+ * model is bounded first (a list whose n overruns a partition is IPLS_E_RANGE
+ * with nothing written on any shard; for get_partitions_segs n < the flat size
+ * is IPLS_E_RANGE, and values beyond the model size are not written), then the
+ * owned / partition list is checked, then the segments, and only then comes
+ * the first launch.  Locking, the fold of queued arrivals before an update and
+ * stream ordering of device outputs are those of ipls_agg_update_gradient,
+ * ipls_agg_send_gradients and ipls_agg_get_partitions with a DEV kind.  On a
+ * handle over several GPUs each shard takes the part of the list that meets
+ * its flat segment; every array a shard touches must be memory its device can
+ * reach (IPLS_E_DEVICE otherwise, before anything is written).
+ * send_gradients_segs with out == NULL returns the sizes only. */
+int ipls_agg_update_gradient_segs(ipls_agg *h, const void *const *ptrs, const int64_t *ns, const int32_t *kinds,
+                                  int n_segs, const int32_t *owned, int n_owned);
+int64_t ipls_agg_send_gradients_segs(ipls_agg *h, const void *const *ptrs, const int64_t *ns, const int32_t *kinds,
+                                     int n_segs, const int32_t *parts, int n_parts, int32_t iteration, int16_t pid,
+                                     const uint8_t *origin, int32_t origin_len,
+                                     void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
+int ipls_agg_get_partitions_segs(ipls_agg *h, void *const *ptrs, const int64_t *ns, const int32_t *kinds, int n_segs);
+
 /* ---- observability ----
  * What the last fold launch of a handle (of p's shard for multi-GPU handles:
  * the shard of the last call) ran: the kernel, the tile shape chosen by the
@@ -854,6 +901,21 @@ int64_t ipls_agg_send_gradients(ipls_agg *h, const void *flat, int64_t n, int sr
                                         `vectors` = 4 source elements; grid = blocks x jobs; shape 0; seqf 1 when
                                         at least one lane of one job took the fast path, else 0; be_in as for the
                                         fold kernels */
+/* The segment-list kernels: block x vectors is the tile in elements, laid over the destination, the same for
+ * every element format; grid is the blocks (items) of the call's last launch.  (Enumerators, not macros: the
+ * macro list above is the set of kernels of the flat vector calls, which stays as it is.) */
+enum {
+    IPLS_KERNEL_UPDATE_SEGS = 13,    /* k_update_segs (update_gradient_segs): one launch per shard and repeat
+                                        level, one block per accumulator tile; seqf 1 when at least one block
+                                        took the vector body (a full tile inside one segment), else 0; start as
+                                        for IPLS_KERNEL_UPDATE_FLAT */
+    IPLS_KERNEL_DIVIDE_SEGS = 14,    /* k_divide_segs (get_partitions_segs): one block per tile of an output
+                                        segment (its head up to the first 128-B line is a block of its own);
+                                        seqf 1 when at least one block took the vector body */
+    IPLS_KERNEL_ENCODE_SEGS = 15     /* k_b64url_encode_segs (send_gradients_segs): as IPLS_KERNEL_ENCODE_FLAT;
+                                        a lane writes the text of 24 frame bytes = `vectors` = 3 payload values;
+                                        seqf 1 when at least one lane had its four values in one segment */
+};
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2
 #define IPLS_SHAPE_SMALL  3

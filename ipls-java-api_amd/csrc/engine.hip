@@ -35,11 +35,13 @@
 
 #include "../../include/ipls_agg.h"
 #include "ipls_kernels.hpp"
+#include "seg_kernels.hpp"
 #include "javaser.hpp"
 #include "engine.hpp"
 #include "operand.hpp"
 #include "pubsub_host.hpp"
 #include "reduce_plan.hpp"
+#include "seg_plan.hpp"
 #include "stage.hpp"
 
 using namespace ipls;
@@ -3214,6 +3216,209 @@ int64_t dev_send_many(ipls_dev* h, const void* flat, int64_t n, int src_kind, in
     });
   HIP_TRY(h, hipGetLastError());
   h->last_launch = launch_info(IPLS_KERNEL_ENCODE_FLAT, 0, kBlock, 4, any_fast ? 1 : 0, 0, (int64_t)gx * n_parts, be_in,
+                               false, 0);
+  if (direct) return IPLS_OK;                           // stream-ordered
+  const hipMemcpyKind kind = out_kind == IPLS_DEV_TEXT ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  for (int i = 0; i < n_parts; ++i)
+    HIP_TRY(h, hipMemcpyAsync((unsigned char*)out + offs[i], base + offs[i], (size_t)lens[i], kind, h->stream));
+  if (out_kind == IPLS_HOST_TEXT) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return IPLS_OK;
+}
+
+// ---- the segment-list calls (engine.hpp; seg_plan.hpp plans, seg_kernels.hpp runs) ----
+namespace {
+// Several tables of one launch in one upload: each starts 16-B aligned.
+struct TablePack {
+  std::vector<unsigned char> bytes;
+  template <class T>
+  size_t add(const T* v, size_t n) {
+    const size_t at = (bytes.size() + 15) / 16 * 16;
+    bytes.resize(at + std::max<size_t>(n * sizeof(T), 16));
+    if (n) std::memcpy(bytes.data() + at, v, n * sizeof(T));
+    return at;
+  }
+};
+
+segplan::Geometry seg_geometry(const ipls_dev* h) {
+  segplan::Geometry g;
+  g.P = h->P;
+  g.chunk = h->chunk;
+  g.off = h->flat_off.data();
+  g.len = h->len.data();
+  g.flat_base = h->flat_base;
+  g.flat_total = h->flat_total;
+  return g;
+}
+std::vector<segplan::Seg> seg_table(const seg_ref* segs, int n_segs) {
+  std::vector<segplan::Seg> v((size_t)std::max(n_segs, 0));
+  for (int s = 0; s < n_segs; ++s) {
+    v[(size_t)s].n = segs[s].n;
+    v[(size_t)s].fmt = segs[s].fmt;
+    v[(size_t)s].mod = (int)((uintptr_t)segs[s].ptr & 127);
+  }
+  return v;
+}
+std::vector<SegPiece> seg_pieces(const segplan::Plan& pl, const seg_ref* segs) {
+  std::vector<SegPiece> v(pl.pieces.size());
+  for (size_t k = 0; k < v.size(); ++k) {
+    const segplan::Piece& p = pl.pieces[k];
+    const seg_ref& sg = segs[p.seg];
+    v[k] = SegPiece{p.dst, p.n, (const char*)sg.ptr + p.src * segplan::fmt_esz(sg.fmt), sg.fmt};
+  }
+  return v;
+}
+// a plan's refusal as the call's (the front has refused a bad table before)
+int seg_plan_rc(ipls_dev* h, const segplan::Plan& pl) {
+  switch (pl.status) {
+    case segplan::kOk: return IPLS_OK;
+    case segplan::kOverrun:
+      return fail(h, IPLS_E_RANGE, "gradient list of %lld values overruns partition %d (ArrayIndexOutOfBounds, IPLS.java:1030)",
+                  (long long)pl.n, h->p_lo + pl.bad);
+    case segplan::kBadPartition: return fail(h, IPLS_E_RANGE, "partition %d out of range [0,%d)", pl.bad, h->P);
+    case segplan::kShort:
+      return fail(h, IPLS_E_RANGE, "output list of %lld < model size %lld", (long long)pl.n, (long long)h->flat_total);
+    default: return fail(h, IPLS_E_INVAL, "bad segment list");
+  }
+}
+}  // namespace
+
+int dev_update_gradient_segs(ipls_dev* h, const seg_ref* segs, int n_segs, const int32_t* owned, int n_owned) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  IPLS_LOCK(h);
+  const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
+  const segplan::Plan pl = segplan::plan_update(seg_geometry(h), tab.data(), n_segs, owned, n_owned, kSegTile);
+  if (int rc = seg_plan_rc(h, pl)) return rc;
+  if (n_owned == 0) return IPLS_OK;
+  HIP_TRY(h, dev_use(h->device));
+  const std::vector<SegPiece> pieces = seg_pieces(pl, segs);
+  for (const segplan::Launch& l : pl.launches) {
+    std::vector<SegJob> jobs(l.jobs.size());
+    bool all_zero = true;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+      const int q = l.jobs[j].q;
+      jobs[j] = SegJob{(unsigned long long*)(h->arena + h->agg_off[q]), l.jobs[j].ncopy, l.jobs[j].L, h->agg_zero[q]};
+      all_zero = all_zero && h->agg_zero[q];
+    }
+    TablePack pack;
+    const size_t at_items = pack.add(l.items.data(), l.items.size());
+    const size_t at_jobs = pack.add(jobs.data(), jobs.size());
+    const size_t at_pieces = pack.add(pieces.data(), pieces.size());
+    void* d = nullptr;
+    if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &d)) return rc;
+    const char* dt = (const char*)d;
+    hipLaunchKernelGGL(k_update_segs, dim3((unsigned)l.items.size()), dim3(kBlock), 0, h->stream,
+                       (const segplan::Item*)(dt + at_items), (const SegJob*)(dt + at_jobs),
+                       (const SegPiece*)(dt + at_pieces));
+    HIP_TRY(h, hipGetLastError());
+    for (const segplan::Job& j : l.jobs) h->agg_zero[j.q] = 0;
+    h->last_launch = launch_info(IPLS_KERNEL_UPDATE_SEGS, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
+                                 (int64_t)l.items.size(), false, false, all_zero ? kZero : kAccum);
+  }
+  return IPLS_OK;
+}
+
+int dev_get_partitions_segs(ipls_dev* h, const seg_ref* segs, int n_segs) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  IPLS_LOCK(h);
+  const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
+  const segplan::Plan pl = segplan::plan_divide(seg_geometry(h), tab.data(), n_segs, kSegTile);
+  if (int rc = seg_plan_rc(h, pl)) return rc;
+  const segplan::Launch& l = pl.launches[0];
+  if (l.items.empty()) return IPLS_OK;
+  HIP_TRY(h, dev_use(h->device));
+  std::vector<void*> outs((size_t)n_segs);
+  for (int s = 0; s < n_segs; ++s) outs[(size_t)s] = const_cast<void*>(segs[s].ptr);
+  std::vector<SegDivPart> parts((size_t)h->P);
+  for (int q = 0; q < h->P; ++q) parts[(size_t)q] = SegDivPart{h->arena + h->w_off[q], h->len[q]};
+  TablePack pack;
+  const size_t at_items = pack.add(l.items.data(), l.items.size());
+  const size_t at_outs = pack.add(outs.data(), outs.size());
+  const size_t at_parts = pack.add(parts.data(), parts.size());
+  void* d = nullptr;
+  if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &d)) return rc;
+  const char* dt = (const char*)d;
+  with_bool(h->secure != 0, [&](auto sec) {
+    hipLaunchKernelGGL((k_divide_segs<decltype(sec)::value>), dim3((unsigned)l.items.size()), dim3(kBlock), 0,
+                       h->stream, (const segplan::Item*)(dt + at_items), (void* const*)(dt + at_outs),
+                       (const SegDivPart*)(dt + at_parts), h->chunk, (int64_t)h->p_lo);
+  });
+  HIP_TRY(h, hipGetLastError());
+  h->last_launch = launch_info(IPLS_KERNEL_DIVIDE_SEGS, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
+                               (int64_t)l.items.size(), false, false, 0);
+  return IPLS_OK;
+}
+
+// dev_send_many over a segment list: device sources only, read where they lie.
+int64_t dev_send_many_segs(ipls_dev* h, const seg_ref* segs, int n_segs, int n_parts, const int* parts,
+                           int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
+                           const int64_t* offs, const int64_t* lens, int out_kind) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  // as dev_send_many: no accumulator, zero flag or queue is read or written, so queued arrivals stay queued
+  std::lock_guard<std::mutex> lk_(h->mu);
+  if (n_parts <= 0) return IPLS_OK;
+  if (origin_len < 0 || (origin_len > 0 && !origin)) return fail(h, IPLS_E_INVAL, "bad origin");
+  if (out_kind != IPLS_HOST_TEXT && out_kind != IPLS_DEV_TEXT) return fail(h, IPLS_E_INVAL, "out_kind HOST_TEXT/DEV_TEXT");
+  for (int i = 0; i < n_parts; ++i)
+    if (int rc = check_part(h, parts[i])) return rc;
+  const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
+  const segplan::Plan pl = segplan::plan_send(seg_geometry(h), tab.data(), n_segs, parts, n_parts);
+  if (int rc = seg_plan_rc(h, pl)) return rc;
+  HIP_TRY(h, dev_use(h->device));
+  if (out_kind == IPLS_DEV_TEXT && !kernel_writable(out))
+    return fail(h, IPLS_E_INVAL, "DEV_TEXT output is neither device memory nor pinned host memory");
+  const unsigned char* dorig = nullptr;
+  if (origin_len > 0) {
+    void* d = nullptr;
+    if (int rc = upload_table(h, origin, (size_t)origin_len, &d)) return rc;
+    dorig = (const unsigned char*)d;
+  }
+  // texts land straight in a 16-B aligned device buffer; else in the scratch buffer at the same offsets, then copied out
+  const bool direct = out_kind == IPLS_DEV_TEXT && !((uintptr_t)out & 15);
+  int64_t span = 0;
+  for (int i = 0; i < n_parts; ++i) span = std::max(span, offs[i] + lens[i]);
+  int64_t lo = span;
+  for (int i = 0; i < n_parts; ++i) lo = std::min(lo, offs[i]);
+  if (!direct)
+    if (int rc = ensure_scratch(h, (size_t)align_up(span - lo + 64, 256))) return rc;
+  unsigned char* base = direct ? (unsigned char*)out : (unsigned char*)h->d_scratch - lo;
+  const std::vector<SegPiece> pieces = seg_pieces(pl, segs);
+  const segplan::Launch& l = pl.launches[0];
+  std::vector<SegEncJob> jobs((size_t)n_parts);
+  int64_t max_groups = 1;
+  bool any_fast = false;
+  for (int i = 0; i < n_parts; ++i) {
+    const segplan::Job& pj = l.jobs[(size_t)i];
+    SegEncJob& j = jobs[(size_t)i];
+    j = SegEncJob{};
+    frame_header(j.hdr, pid, pj.L, h->p_lo + pj.q, iteration);
+    j.L = pj.L;
+    j.ncopy = pj.ncopy;
+    j.piece_lo = pj.piece_lo;
+    j.piece_hi = pj.piece_hi;
+    j.origin_len = origin_len;
+    j.origin = dorig;
+    j.out = base + offs[i];
+    j.groups = (14 + 8 * pj.L + origin_len + 23) / 24;
+    j.text_len = lens[i];
+    max_groups = std::max(max_groups, j.groups);
+    // a lane g >= 1 is fast when its values 3g - 2 .. 3g + 1 lie in one piece
+    for (int k = pj.piece_lo; k < pj.piece_hi && !any_fast; ++k) {
+      const segplan::Piece& p = pl.pieces[(size_t)k];
+      const int64_t g = std::max<int64_t>(1, (p.dst + 2 + 2) / 3);
+      any_fast = 3 * g + 2 <= p.dst + p.n;
+    }
+  }
+  TablePack pack;
+  const size_t at_jobs = pack.add(jobs.data(), jobs.size());
+  const size_t at_pieces = pack.add(pieces.data(), pieces.size());
+  void* djobs = nullptr;
+  if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &djobs)) return rc;
+  const unsigned gx = std::max(1u, std::min<unsigned>(blocks_for(max_groups, kBlock), 16384));
+  const dim3 grid(gx, (unsigned)n_parts);
+  hipLaunchKernelGGL(k_b64url_encode_segs, grid, dim3(kBlock), 0, h->stream,
+                     (const SegEncJob*)((const char*)djobs + at_jobs), (const SegPiece*)((const char*)djobs + at_pieces));
+  HIP_TRY(h, hipGetLastError());
+  h->last_launch = launch_info(IPLS_KERNEL_ENCODE_SEGS, 0, kBlock, 3, any_fast ? 1 : 0, 0, (int64_t)gx * n_parts, false,
                                false, 0);
   if (direct) return IPLS_OK;                           // stream-ordered
   const hipMemcpyKind kind = out_kind == IPLS_DEV_TEXT ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;

@@ -143,6 +143,22 @@ int64_t dev_send_many(ipls_dev* h, const void* flat, int64_t n, int src_kind, in
                       int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
                       const int64_t* offs, const int64_t* lens, int out_kind);
 
+// ---- the segment-list calls (ipls_agg_*_segs; seg_plan.hpp, seg_kernels.hpp) ----
+// The flat vector is the concatenation of n_segs device arrays.  The front has
+// validated the table (kinds, alignment, lengths); the engine plans its own
+// part -- the segments that meet its flat segment -- and launches once per
+// repeat level (update), once (divide, send).  fmt: a segplan format code.
+struct seg_ref {
+  const void* ptr;
+  int64_t n;
+  int fmt;
+};
+int dev_update_gradient_segs(ipls_dev* h, const seg_ref* segs, int n_segs, const int32_t* owned, int n_owned);
+int dev_get_partitions_segs(ipls_dev* h, const seg_ref* segs, int n_segs);
+int64_t dev_send_many_segs(ipls_dev* h, const seg_ref* segs, int n_segs, int n_parts, const int* parts,
+                           int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
+                           const int64_t* offs, const int64_t* lens, int out_kind);
+
 // ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
 // One run of a file that an engine packs: `prefix` (framing), then engine
 // partition q's values of `target`, then `suffix` (a byte, or -1).

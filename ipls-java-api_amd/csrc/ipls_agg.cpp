@@ -47,6 +47,7 @@
 #include "javaser.hpp"
 #include "operand.hpp"
 #include "pubsub_host.hpp"
+#include "seg_plan.hpp"
 
 namespace {
 
@@ -1382,6 +1383,172 @@ int64_t ipls_agg_send_gradients(ipls_agg* H, const void* flat, int64_t n, int sr
     H->last_shard = s;
     if (int64_t rc = dev_send_many(H->sh[s], flat, n, src_kind, (int)lp.size(), lp.data(), iteration, pid, origin,
                                    origin_len, out, oo.data(), ll.data(), out_kind);
+        rc < 0)
+      return fwd(H, s, (int)rc);
+  }
+  return total;
+}
+
+// ---- the segment-list calls: the trainer boundary over a list of arrays ----
+namespace {
+
+// The table's shape (before anything else is looked at) and the number of
+// values it holds; a negative length counts as none here and is refused by
+// segs_check, after the partitions and the owned / partition list.
+int segs_total(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds, int n_segs,
+               int64_t* total) {
+  if (n_segs < 0 || (n_segs > 0 && (!ptrs || !ns || !kinds))) return ferr(H, IPLS_E_INVAL, "bad segment table");
+  int64_t t = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    if (ns[s] <= 0) continue;
+    if (ns[s] > INT64_MAX - t) return ferr(H, IPLS_E_RANGE, "segment list longer than 2^63 values");
+    t += ns[s];
+  }
+  *total = t;
+  return IPLS_OK;
+}
+
+int segs_check(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds, int n_segs,
+               std::vector<seg_ref>& out) {
+  namespace sp = ipls::segplan;
+  out.resize((size_t)n_segs);
+  for (int s = 0; s < n_segs; ++s) {
+    const int k = kinds[s];
+    const int fmt = k == IPLS_DEV_F64 ? sp::kF64 : k == IPLS_DEV_F32 ? sp::kF32 : k == IPLS_DEV_F16 ? sp::kF16
+                    : k == IPLS_DEV_BF16 ? sp::kBF16 : -1;
+    if (fmt < 0) return ferr(H, IPLS_E_INVAL, "segment %d: kind %d is not DEV_F64 / DEV_F32 / DEV_F16 / DEV_BF16", s, k);
+    if (ns[s] < 0) return ferr(H, IPLS_E_INVAL, "segment %d: negative length %lld", s, (long long)ns[s]);
+    if (ns[s] > 0 && !ptrs[s]) return ferr(H, IPLS_E_INVAL, "segment %d: null pointer", s);
+    const int esz = sp::fmt_esz(fmt);
+    if (ns[s] > 0 && ((uintptr_t)ptrs[s] & (uintptr_t)(esz - 1)))
+      return ferr(H, IPLS_E_INVAL, "segment %d: pointer not %d-byte aligned", s, esz);
+    // an empty segment's pointer is never looked at again
+    out[(size_t)s] = seg_ref{ns[s] > 0 ? ptrs[s] : nullptr, ns[s], fmt};
+  }
+  return IPLS_OK;
+}
+
+// OrganizeGradients splits EVERY partition before anything is accumulated or sent
+int segs_bounds(ipls_agg* H, int64_t n) {
+  for (int p = 0; p < H->P; ++p) {
+    const int64_t nc = std::max<int64_t>(0, std::min(H->off[p] + H->chunk, n) - H->off[p]);
+    if (nc > H->len[p] - 1)
+      return ferr(H, IPLS_E_RANGE, "gradient list of %lld values overruns partition %d "
+                  "(ArrayIndexOutOfBounds, IPLS.java:1030)", (long long)n, p);
+  }
+  return IPLS_OK;
+}
+
+// Multi-shard handles: every segment that meets flat [a, b) is read or written by shard s's device.
+int segs_reach(ipls_agg* H, int s, const std::vector<seg_ref>& segs, int64_t a, int64_t b, const char* what) {
+  int64_t at = 0;
+  for (const seg_ref& g : segs) {
+    if (g.n > 0 && at < b && at + g.n > a)
+      if (int rc = check_reach(H, s, g.ptr, what)) return rc;
+    at += g.n;
+  }
+  return IPLS_OK;
+}
+
+}  // namespace
+
+int ipls_agg_update_gradient_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
+                                  int n_segs, const int32_t* owned, int n_owned) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  int64_t n = 0;
+  if (int rc = segs_total(H, ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (int rc = segs_bounds(H, n)) return rc;
+  if (n_owned < 0 || (n_owned > 0 && !owned)) return ferr(H, IPLS_E_INVAL, "bad owned list");
+  for (int i = 0; i < n_owned; ++i)
+    if (!part_ok(H, owned[i])) return range_err(H, owned[i]);
+  std::vector<seg_ref> segs;
+  if (int rc = segs_check(H, ptrs, ns, kinds, n_segs, segs)) return rc;
+  if (n_owned == 0) return IPLS_OK;
+  std::vector<std::vector<int32_t>> per(H->S());
+  for (int i = 0; i < n_owned; ++i) per[H->owner[owned[i]]].push_back(owned[i] - H->lo[H->owner[owned[i]]]);
+  std::vector<int> ss;
+  for (int s = 0; s < H->S(); ++s)
+    if (!per[s].empty()) ss.push_back(s);
+  if (H->S() > 1)
+    for (int s : ss)
+      if (int rc = segs_reach(H, s, segs, H->off[H->lo[s]], H->off[H->lo[s + 1] - 1] + H->chunk, "gradient segment"))
+        return rc;
+  H->last_shard.store(ss.back(), std::memory_order_relaxed);
+  return par_shards(H, ss, [&](int s) {
+    return dev_update_gradient_segs(H->sh[s], segs.data(), n_segs, per[s].data(), (int)per[s].size());
+  });
+}
+
+int ipls_agg_get_partitions_segs(ipls_agg* H, void* const* ptrs, const int64_t* ns, const int32_t* kinds, int n_segs) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  int64_t n = 0;
+  if (int rc = segs_total(H, ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (n < H->flat_total)
+    return ferr(H, IPLS_E_RANGE, "output list of %lld < model size %lld", (long long)n, (long long)H->flat_total);
+  std::vector<seg_ref> segs;
+  if (int rc = segs_check(H, ptrs, ns, kinds, n_segs, segs)) return rc;
+  const std::vector<int> ss = nonempty_shards(H);
+  if (ss.empty()) return IPLS_OK;
+  if (H->S() > 1)
+    for (int s : ss)
+      if (int rc = segs_reach(H, s, segs, H->off[H->lo[s]], H->off[H->lo[s + 1] - 1] + H->chunk, "output segment"))
+        return rc;
+  H->last_shard.store(ss.back(), std::memory_order_relaxed);
+  // every shard writes its flat segment [off[lo_s], ...) of the model
+  return par_shards(H, ss, [&](int s) { return dev_get_partitions_segs(H->sh[s], segs.data(), n_segs); });
+}
+
+int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
+                                     int n_segs, const int32_t* parts, int n_parts, int32_t iteration, int16_t pid,
+                                     const uint8_t* origin, int32_t origin_len, void* out, int64_t out_cap,
+                                     int out_kind, int64_t* lens, int64_t* offs) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  int64_t n = 0;
+  if (int rc = segs_total(H, ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (n_parts < 0 || (n_parts > 0 && !parts)) return ferr(H, IPLS_E_INVAL, "bad partition list");
+  if (origin_len < 0 || (out && origin_len > 0 && !origin)) return ferr(H, IPLS_E_INVAL, "bad origin");
+  if (out_kind != IPLS_HOST_TEXT && out_kind != IPLS_DEV_TEXT) return ferr(H, IPLS_E_INVAL, "out_kind HOST_TEXT/DEV_TEXT");
+  std::vector<int64_t> L(n_parts), O(n_parts);
+  int64_t total = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    if (!part_ok(H, parts[i])) return range_err(H, parts[i]);
+    O[i] = (total + 63) / 64 * 64;                        // every text 64-B aligned
+    L[i] = ipls::pubsub::b64_enc_len(14 + 8 * H->len[parts[i]] + origin_len);
+    total = O[i] + L[i];
+  }
+  if (lens) std::copy(L.begin(), L.end(), lens);
+  if (offs) std::copy(O.begin(), O.end(), offs);
+  if (!out || n_parts == 0) return total;
+  if (int rc = segs_bounds(H, n)) return rc;
+  if (out_cap < total) return ferr(H, IPLS_E_RANGE, "gradient texts need %lld bytes", (long long)total);
+  std::vector<seg_ref> segs;
+  if (int rc = segs_check(H, ptrs, ns, kinds, n_segs, segs)) return rc;
+  // group by owner shard; each shard encodes its texts in one launch
+  std::vector<std::vector<int>> idx(H->S());
+  for (int i = 0; i < n_parts; ++i) idx[H->owner[parts[i]]].push_back(i);
+  if (H->S() > 1)
+    for (int s = 0; s < H->S(); ++s) {
+      if (idx[s].empty()) continue;
+      if (out_kind == IPLS_DEV_TEXT)
+        if (int rc = check_reach(H, s, out, "text buffer")) return rc;
+      if (int rc = segs_reach(H, s, segs, H->off[H->lo[s]], H->off[H->lo[s + 1] - 1] + H->chunk, "gradient segment"))
+        return rc;
+    }
+  for (int s = 0; s < H->S(); ++s) {
+    if (idx[s].empty()) continue;
+    std::vector<int> lp;
+    std::vector<int64_t> oo, ll;
+    for (int i : idx[s]) {
+      lp.push_back(parts[i] - H->lo[s]);
+      oo.push_back(O[i]);
+      ll.push_back(L[i]);
+    }
+    H->last_shard = s;
+    if (int64_t rc = dev_send_many_segs(H->sh[s], segs.data(), n_segs, (int)lp.size(), lp.data(), iteration, pid,
+                                        origin, origin_len, out, oo.data(), ll.data(), out_kind);
         rc < 0)
       return fwd(H, s, (int)rc);
   }

@@ -34,6 +34,8 @@ KERNEL_ROUND_F32, KERNEL_ROUND_H16 = 7, 8
 KERNEL_FOLD1_F32, KERNEL_FOLD1_H16 = 9, 10   # k_fold1_narrow: one trainer-format arrival
 KERNEL_UPDATE_FLAT = 11                      # k_update_flat: one whole streamed gradient (update_gradient_chunked)
 KERNEL_ENCODE_FLAT = 12                      # k_b64url_encode_flat: a flat gradient's partitions as texts (send_gradients)
+# the segment-list calls (k_update_segs, k_divide_segs, k_b64url_encode_segs): a list of tensors in or out
+KERNEL_UPDATE_SEGS, KERNEL_DIVIDE_SEGS, KERNEL_ENCODE_SEGS = 13, 14, 15
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -164,6 +166,11 @@ SIGNATURES = {
     "ipls_agg_publish_partial": (_i64, [_vp, _i, _i, _i32, _i32, _i16, _vp, _i32, _vp, _i64, _i]),
     "ipls_agg_publish_partials": (_i64, [_vp, _vp, _i, _i, _i32, _vp, _i16, _vp, _i32, _vp, _i64, _i, _vp, _vp]),
     "ipls_agg_send_gradients": (_i64, [_vp, _vp, _i64, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp, _i64, _i, _vp, _vp]),
+    # segment lists: ptrs is void*[], ns int64[], kinds int32[] (ctypes arrays, passed as pointers)
+    "ipls_agg_update_gradient_segs": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i]),
+    "ipls_agg_send_gradients_segs": (_i64, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp, _i64, _i,
+                                            _vp, _vp]),
+    "ipls_agg_get_partitions_segs": (_i, [_vp, _vp, _vp, _vp, _i]),
     "ipls_agg_last_launch": (_i, [_vp, _P(LaunchInfo)]),
     # saved-model files; the host-only encoders take typed first pointers (NULL is a valid empty input)
     "ipls_saved_parse": (_i64, [_vp, _i64, _P(_i32), _P(_i64), _P(_i64), _i64]),

@@ -94,6 +94,61 @@ _HOST_KIND = {"f32": N.HOST_F32, "half": N.HOST_F16, "bf16": N.HOST_BF16}
 _NOUN = {"f64": "doubles", "f32": "floats", "half": "halves", "bf16": "bfloat16s"}
 
 
+_SEG_KIND = {"torch.float64": N.DEV_F64, "torch.float32": N.DEV_F32, "torch.float16": N.DEV_F16,
+             "torch.bfloat16": N.DEV_BF16}
+
+
+class Segments:
+    """A flat vector given as a LIST of device tensors (a model's parameters,
+    or their gradients): the concatenation of the tensors in list order, each
+    read in memory order -- ``parameters_to_vector`` order -- without the
+    ``torch.cat`` that would build it or the copy-out that would scatter it
+    (include/ipls_agg.h, the ``_segs`` calls).  ``from_tensors`` builds the
+    three tables the library takes once; the object keeps the tensors alive
+    and can be passed again every step.  ``n`` is the number of values,
+    ``n_segs`` the number of tensors, ``tensors`` the tuple itself.  As with
+    DeviceBuffer, what torch wrote must be complete before the call."""
+
+    def __init__(self, tensors, ptrs, ns, kinds):
+        self.tensors, self._ptrs, self._ns, self._kinds = tensors, ptrs, ns, kinds
+        self.n_segs = len(tensors)
+        self.n = int(sum(ns))
+
+    @classmethod
+    def from_tensors(cls, tensors) -> "Segments":
+        """Contiguous CUDA tensors of float64 / float32 / float16 / bfloat16,
+        mixed freely; ``numel() == 0`` is allowed.  Anything else -- a CPU
+        tensor, a non-contiguous one, another dtype -- is a ValueError before
+        any library call: no silent copy is made."""
+        tensors = tuple(tensors)
+        for i, t in enumerate(tensors):
+            if not getattr(t, "is_cuda", False):
+                raise ValueError(f"tensor {i}: need a CUDA tensor")
+            if not t.is_contiguous():
+                raise ValueError(f"tensor {i}: need a contiguous tensor (no silent copy is made)")
+            if str(t.dtype) not in _SEG_KIND:
+                raise ValueError(f"tensor {i}: dtype {t.dtype} is not float64, float32, float16 or bfloat16")
+        k = len(tensors)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[int(t.data_ptr()) if t.numel() else None for t in tensors])
+        ns = (ctypes.c_int64 * max(k, 1))(*[t.numel() for t in tensors])
+        kinds = (ctypes.c_int32 * max(k, 1))(*[_SEG_KIND[str(t.dtype)] for t in tensors])
+        return cls(tensors, ptrs, ns, kinds)
+
+    @property
+    def tables(self):
+        """(ptrs, ns, kinds, n_segs) as the C calls take them."""
+        return self._ptrs, self._ns, self._kinds, self.n_segs
+
+
+def _segments(x):
+    """x as a Segments when it is one, or a list / tuple of CUDA tensors (wrapped on the fly); else None."""
+    if isinstance(x, Segments):
+        return x
+    if isinstance(x, (list, tuple)) and x and all(getattr(t, "is_cuda", False) for t in x):
+        return Segments.from_tensors(x)
+    return None
+
+
 def _out_dtype(dtype):
     """'f64', 'f32', 'half' or 'bf16' for the ``dtype=`` of GetPartitions /
     aggregate_round: a numpy dtype, or the string "bf16" (numpy has no
@@ -314,7 +369,18 @@ class Aggregator:
     def InitializeWeights(self, model, big_endian: bool = False, *, java_list: bool = False):
         """IPLS.java:1880-1901 (model = List<Double>, or read_file's raw BE
         bytes; ``java_list=True``: the bytes of a Java-serialised
-        ArrayList<Double>, what DownloadParameters reads, IPLS.java:567)."""
+        ArrayList<Double>, what DownloadParameters reads, IPLS.java:567).
+        A ``Segments`` (the model as its list of parameter tensors) is
+        concatenated as doubles on the device here, in the binding, and loaded
+        through the same call: this happens once per run, so it has no list
+        form in the C-ABI."""
+        if isinstance(model, Segments):
+            import torch
+            flat = (torch.cat([t.reshape(-1).double() for t in model.tensors]) if model.n_segs
+                    else torch.empty(0, dtype=torch.float64, device="cuda"))
+            torch.cuda.synchronize(flat.device)
+            self._chk(self._lib.ipls_agg_load_model(self._h, int(flat.data_ptr()) or None, flat.numel(), N.DEV_F64))
+            return
         if java_list:
             keep = _u8(model)
             ptr, n, kind = keep.ctypes.data, keep.size, N.HOST_DLIST
@@ -340,9 +406,16 @@ class Aggregator:
 
     def UpdateGradient(self, gradients, auth_list):
         """Own-partition accumulate of IPLS.UpdateGradient (IPLS.java:1737-1743).
-        ``gradients=None`` is the "did not train in time" call (no-op)."""
+        ``gradients=None`` is the "did not train in time" call (no-op).  A
+        ``Segments``, or a plain list / tuple of CUDA tensors (the gradients
+        as autograd left them, mixed dtypes allowed), is read where the
+        tensors lie: no ``torch.cat``, no cast pass."""
         owned = np.ascontiguousarray(np.asarray(list(auth_list), dtype=np.int32))
         if gradients is None:
+            return
+        segs = _segments(gradients)
+        if segs is not None:   # a list of device tensors, read where they lie (k_update_segs)
+            self._chk(self._lib.ipls_agg_update_gradient_segs(self._h, *segs.tables, owned.ctypes.data, len(owned)))
             return
         ptr, n, kind, keep = _operand(gradients, f32=True)
         self._chk(self._lib.ipls_agg_update_gradient(
@@ -870,8 +943,13 @@ class Aggregator:
         half / bf16 DeviceBuffer, ``dtype=np.float16`` (a numpy float16 array)
         or ``dtype="bf16"`` (a numpy uint16 array of the bfloat16 bit
         patterns) gets that float rounded again to the 16-bit format, 2 bytes
-        per value."""
+        per value.  A ``Segments`` ``out`` (the model's parameter tensors)
+        gets every tensor written in its own dtype by those same rules, with
+        no flat model and no copy-out in between."""
         n = self.flat_size
+        if isinstance(out, Segments):   # straight into the model's tensors, each in its own dtype (k_divide_segs)
+            self._chk(self._lib.ipls_agg_get_partitions_segs(self._h, *out.tables))
+            return out
         if isinstance(out, DeviceBuffer):
             self._chk(self._lib.ipls_agg_get_partitions(self._h, out.ptr, out.n, _DEV_KIND.get(out.dtype, N.DEV_F64)))
             return out
@@ -1040,7 +1118,9 @@ class Aggregator:
         iteration, pid)), encoded on the GPU straight from the flat vector in
         one launch per GPU.  ``gradients`` is what UpdateGradient takes (numpy
         float64 / float32 / float16, a CPU torch tensor, a DeviceBuffer), or
-        ``None`` for the "did not train in time" texts (n = 0).  A -0.0 stays
+        ``None`` for the "did not train in time" texts (n = 0), or a
+        ``Segments`` / list / tuple of CUDA tensors, encoded straight from the
+        tensors.  A -0.0 stays
         -0.0 and the count slot is generated; the text is one base64 layer
         (the pubsub transport adds the second); secure mode's Encode is the
         caller's.  Returns the list of texts (bytes), or, when ``out`` is a
@@ -1049,7 +1129,8 @@ class Aggregator:
         parts = np.ascontiguousarray(list(partitions), dtype=np.int32)
         o = np.frombuffer(bytes(origin), dtype=np.uint8)
         op = o.ctypes.data if o.size else None
-        if gradients is None:
+        segs = _segments(gradients)
+        if segs is not None or gradients is None:
             ptr, ng, kind, keep = None, 0, N.HOST_F64, None
         else:
             if getattr(gradients, "is_cuda", False):   # a GPU torch tensor: read where it lies
@@ -1060,6 +1141,9 @@ class Aggregator:
         offs = np.zeros(max(1, n), dtype=np.int64)
 
         def call(dst, cap, dst_kind, le=None, of=None):
+            if segs is not None:   # a list of device tensors, read where they lie (k_b64url_encode_segs)
+                return self._chk(self._lib.ipls_agg_send_gradients_segs(
+                    self._h, *segs.tables, parts.ctypes.data, n, iteration, pid, op, o.size, dst, cap, dst_kind, le, of))
             return self._chk(self._lib.ipls_agg_send_gradients(
                 self._h, ptr, ng, kind, parts.ctypes.data, n, iteration, pid, op, o.size, dst, cap, dst_kind, le, of))
 
