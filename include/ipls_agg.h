@@ -868,6 +868,52 @@ int64_t ipls_agg_send_gradients_segs(ipls_agg *h, const void *const *ptrs, const
                                      void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
 int ipls_agg_get_partitions_segs(ipls_agg *h, void *const *ptrs, const int64_t *ns, const int32_t *kinds, int n_segs);
 
+/* ---- the trainer's update as the DIFFERENCE of two lists ----
+ *
+ * What the reference trainer hands to UpdateModel is GetDiff(model.params(),
+ * Dumm) (Model.java:413, body :126-128) = Dumm.sub(model.params()):
+ * Difference(received_model, trained_params), element by element, the
+ * subtraction made in the arrays' own data type and only the result widened.
+ * A DIFFERENCE LIST is a segment list with two pointer tables over one ns /
+ * kinds table: a_ptrs[s] the minuend, b_ptrs[s] the subtrahend, lengths and
+ * kinds equal by construction.  Value f = start_s + e of the flat vector it
+ * stands for is (double) sub_k(a[s][e], b[s][e]):
+ *   IPLS_DEV_F64          the IEEE double a - b;
+ *   IPLS_DEV_F32          the float a - b, rounded once to float, then widened
+ *                         exactly; a subnormal result is kept (no flush);
+ *   IPLS_DEV_F16, _BF16   (float)a - (float)b in float, rounded to
+ *                         nearest-even into the format, then widened by the
+ *                         rule of that kind; subnormals are kept, a half
+ *                         result beyond +-65504 is +-inf (what torch.sub and
+ *                         numpy's float16 subtraction give).
+ * x - x is +0.0; (-0.0) - (+0.0) is -0.0 and stays -0.0 in a text; a NaN the
+ * subtraction makes (inf - inf) is a NaN like any other.  No contraction, no
+ * fast-math.  The library takes no side on which list is "the model".
+ *   ipls_agg_update_gradient_segs_diff  the accumulators end with the bits of
+ *       ipls_agg_update_gradient(IPLS_DEV_F64) fed the widened difference;
+ *   ipls_agg_send_gradients_segs_diff   the texts of ipls_agg_send_gradients
+ *       fed the same vector.
+ * Everything else is the _segs twins', word for word: count slot and zero
+ * tail, order of checks (wherever a list is looked at, the minuend list, then
+ * the subtrahend list), all-or-nothing on every shard, locking, the fold of
+ * queued arrivals before an update, stream ordering, out == NULL for the sizes
+ * only, n_segs == 0 as the vector of no values; on a handle over several GPUs
+ * every array of EITHER list that a shard touches must be memory its device
+ * can reach (IPLS_E_DEVICE before anything is written).  A NULL b_ptrs with
+ * n_segs > 0 is IPLS_E_INVAL; a NULL or misaligned pointer of a non-empty
+ * segment in either list is IPLS_E_INVAL, the message naming the segment and
+ * the list ("minuend" / "subtrahend").  The two lists may alias each other and
+ * themselves.  Pairs of different kinds, host lists and a difference OUTPUT
+ * list do not exist. */
+int ipls_agg_update_gradient_segs_diff(ipls_agg *h, const void *const *a_ptrs, const void *const *b_ptrs,
+                                       const int64_t *ns, const int32_t *kinds, int n_segs,
+                                       const int32_t *owned, int n_owned);
+int64_t ipls_agg_send_gradients_segs_diff(ipls_agg *h, const void *const *a_ptrs, const void *const *b_ptrs,
+                                          const int64_t *ns, const int32_t *kinds, int n_segs,
+                                          const int32_t *parts, int n_parts, int32_t iteration, int16_t pid,
+                                          const uint8_t *origin, int32_t origin_len,
+                                          void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
+
 /* ---- observability ----
  * What the last fold launch of a handle (of p's shard for multi-GPU handles:
  * the shard of the last call) ran: the kernel, the tile shape chosen by the
@@ -912,9 +958,13 @@ enum {
     IPLS_KERNEL_DIVIDE_SEGS = 14,    /* k_divide_segs (get_partitions_segs): one block per tile of an output
                                         segment (its head up to the first 128-B line is a block of its own);
                                         seqf 1 when at least one block took the vector body */
-    IPLS_KERNEL_ENCODE_SEGS = 15     /* k_b64url_encode_segs (send_gradients_segs): as IPLS_KERNEL_ENCODE_FLAT;
+    IPLS_KERNEL_ENCODE_SEGS = 15,    /* k_b64url_encode_segs (send_gradients_segs): as IPLS_KERNEL_ENCODE_FLAT;
                                         a lane writes the text of 24 frame bytes = `vectors` = 3 payload values;
                                         seqf 1 when at least one lane had its four values in one segment */
+    IPLS_KERNEL_UPDATE_SEGS_DIFF = 16, /* k_update_segs_diff (update_gradient_segs_diff): every field as for
+                                        IPLS_KERNEL_UPDATE_SEGS */
+    IPLS_KERNEL_ENCODE_SEGS_DIFF = 17  /* k_b64url_encode_segs_diff (send_gradients_segs_diff): every field as for
+                                        IPLS_KERNEL_ENCODE_SEGS */
 };
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2

@@ -36,6 +36,7 @@
 #include "../../include/ipls_agg.h"
 #include "ipls_kernels.hpp"
 #include "seg_kernels.hpp"
+#include "seg_diff_kernels.hpp"
 #include "javaser.hpp"
 #include "engine.hpp"
 #include "operand.hpp"
@@ -3267,6 +3268,15 @@ std::vector<SegPiece> seg_pieces(const segplan::Plan& pl, const seg_ref* segs) {
   }
   return v;
 }
+// The difference calls: per piece, its first SUBTRAHEND element (the plan is the minuend list's).
+std::vector<const void*> seg_pieces_b(const segplan::Plan& pl, const seg_ref* segs, const void* const* b_ptrs) {
+  std::vector<const void*> v(pl.pieces.size());
+  for (size_t k = 0; k < v.size(); ++k) {
+    const segplan::Piece& p = pl.pieces[k];
+    v[k] = (const char*)b_ptrs[p.seg] + p.src * segplan::fmt_esz(segs[p.seg].fmt);
+  }
+  return v;
+}
 // a plan's refusal as the call's (the front has refused a bad table before)
 int seg_plan_rc(ipls_dev* h, const segplan::Plan& pl) {
   switch (pl.status) {
@@ -3282,7 +3292,9 @@ int seg_plan_rc(ipls_dev* h, const segplan::Plan& pl) {
 }
 }  // namespace
 
-int dev_update_gradient_segs(ipls_dev* h, const seg_ref* segs, int n_segs, const int32_t* owned, int n_owned) {
+// b_ptrs: null, or the subtrahend list of a difference call (one pointer per segment, lengths and formats segs')
+static int update_segs(ipls_dev* h, const seg_ref* segs, const void* const* b_ptrs, int n_segs, const int32_t* owned,
+                       int n_owned) {
   if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
   IPLS_LOCK(h);
   const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
@@ -3291,6 +3303,8 @@ int dev_update_gradient_segs(ipls_dev* h, const seg_ref* segs, int n_segs, const
   if (n_owned == 0) return IPLS_OK;
   HIP_TRY(h, dev_use(h->device));
   const std::vector<SegPiece> pieces = seg_pieces(pl, segs);
+  std::vector<const void*> bsrc;
+  if (b_ptrs) bsrc = seg_pieces_b(pl, segs, b_ptrs);
   for (const segplan::Launch& l : pl.launches) {
     std::vector<SegJob> jobs(l.jobs.size());
     bool all_zero = true;
@@ -3303,18 +3317,35 @@ int dev_update_gradient_segs(ipls_dev* h, const seg_ref* segs, int n_segs, const
     const size_t at_items = pack.add(l.items.data(), l.items.size());
     const size_t at_jobs = pack.add(jobs.data(), jobs.size());
     const size_t at_pieces = pack.add(pieces.data(), pieces.size());
+    const size_t at_bsrc = b_ptrs ? pack.add(bsrc.data(), bsrc.size()) : 0;
     void* d = nullptr;
     if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &d)) return rc;
     const char* dt = (const char*)d;
-    hipLaunchKernelGGL(k_update_segs, dim3((unsigned)l.items.size()), dim3(kBlock), 0, h->stream,
-                       (const segplan::Item*)(dt + at_items), (const SegJob*)(dt + at_jobs),
-                       (const SegPiece*)(dt + at_pieces));
+    if (b_ptrs)
+      hipLaunchKernelGGL(k_update_segs_diff, dim3((unsigned)l.items.size()), dim3(kBlock), 0, h->stream,
+                         (const segplan::Item*)(dt + at_items), (const SegJob*)(dt + at_jobs),
+                         (const SegPiece*)(dt + at_pieces), (const void* const*)(dt + at_bsrc));
+    else
+      hipLaunchKernelGGL(k_update_segs, dim3((unsigned)l.items.size()), dim3(kBlock), 0, h->stream,
+                         (const segplan::Item*)(dt + at_items), (const SegJob*)(dt + at_jobs),
+                         (const SegPiece*)(dt + at_pieces));
     HIP_TRY(h, hipGetLastError());
     for (const segplan::Job& j : l.jobs) h->agg_zero[j.q] = 0;
-    h->last_launch = launch_info(IPLS_KERNEL_UPDATE_SEGS, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
-                                 (int64_t)l.items.size(), false, false, all_zero ? kZero : kAccum);
+    h->last_launch = launch_info(b_ptrs ? IPLS_KERNEL_UPDATE_SEGS_DIFF : IPLS_KERNEL_UPDATE_SEGS, 0, kBlock, kSegV,
+                                 l.any_whole ? 1 : 0, 0, (int64_t)l.items.size(), false, false,
+                                 all_zero ? kZero : kAccum);
   }
   return IPLS_OK;
+}
+
+int dev_update_gradient_segs(ipls_dev* h, const seg_ref* segs, int n_segs, const int32_t* owned, int n_owned) {
+  return update_segs(h, segs, nullptr, n_segs, owned, n_owned);
+}
+int dev_update_gradient_segs_diff(ipls_dev* h, const seg_ref* segs, const void* const* b_ptrs, int n_segs,
+                                  const int32_t* owned, int n_owned) {
+  if (n_segs > 0 && !b_ptrs) return fail(h, IPLS_E_INVAL, "null subtrahend list");
+  static const void* const none[1] = {nullptr};
+  return update_segs(h, segs, b_ptrs ? b_ptrs : none, n_segs, owned, n_owned);
 }
 
 int dev_get_partitions_segs(ipls_dev* h, const seg_ref* segs, int n_segs) {
@@ -3349,9 +3380,10 @@ int dev_get_partitions_segs(ipls_dev* h, const seg_ref* segs, int n_segs) {
 }
 
 // dev_send_many over a segment list: device sources only, read where they lie.
-int64_t dev_send_many_segs(ipls_dev* h, const seg_ref* segs, int n_segs, int n_parts, const int* parts,
-                           int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
-                           const int64_t* offs, const int64_t* lens, int out_kind) {
+// b_ptrs: null, or the subtrahend list of a difference call.
+static int64_t send_many_segs(ipls_dev* h, const seg_ref* segs, const void* const* b_ptrs, int n_segs, int n_parts,
+                              const int* parts, int32_t iteration, int16_t pid, const uint8_t* origin,
+                              int32_t origin_len, void* out, const int64_t* offs, const int64_t* lens, int out_kind) {
   if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
   // as dev_send_many: no accumulator, zero flag or queue is read or written, so queued arrivals stay queued
   std::lock_guard<std::mutex> lk_(h->mu);
@@ -3411,21 +3443,44 @@ int64_t dev_send_many_segs(ipls_dev* h, const seg_ref* segs, int n_segs, int n_p
   TablePack pack;
   const size_t at_jobs = pack.add(jobs.data(), jobs.size());
   const size_t at_pieces = pack.add(pieces.data(), pieces.size());
+  std::vector<const void*> bsrc;
+  if (b_ptrs) bsrc = seg_pieces_b(pl, segs, b_ptrs);
+  const size_t at_bsrc = b_ptrs ? pack.add(bsrc.data(), bsrc.size()) : 0;
   void* djobs = nullptr;
   if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &djobs)) return rc;
   const unsigned gx = std::max(1u, std::min<unsigned>(blocks_for(max_groups, kBlock), 16384));
   const dim3 grid(gx, (unsigned)n_parts);
-  hipLaunchKernelGGL(k_b64url_encode_segs, grid, dim3(kBlock), 0, h->stream,
-                     (const SegEncJob*)((const char*)djobs + at_jobs), (const SegPiece*)((const char*)djobs + at_pieces));
+  if (b_ptrs)
+    hipLaunchKernelGGL(k_b64url_encode_segs_diff, grid, dim3(kBlock), 0, h->stream,
+                       (const SegEncJob*)((const char*)djobs + at_jobs), (const SegPiece*)((const char*)djobs + at_pieces),
+                       (const void* const*)((const char*)djobs + at_bsrc));
+  else
+    hipLaunchKernelGGL(k_b64url_encode_segs, grid, dim3(kBlock), 0, h->stream,
+                       (const SegEncJob*)((const char*)djobs + at_jobs), (const SegPiece*)((const char*)djobs + at_pieces));
   HIP_TRY(h, hipGetLastError());
-  h->last_launch = launch_info(IPLS_KERNEL_ENCODE_SEGS, 0, kBlock, 3, any_fast ? 1 : 0, 0, (int64_t)gx * n_parts, false,
-                               false, 0);
+  h->last_launch = launch_info(b_ptrs ? IPLS_KERNEL_ENCODE_SEGS_DIFF : IPLS_KERNEL_ENCODE_SEGS, 0, kBlock, 3,
+                               any_fast ? 1 : 0, 0, (int64_t)gx * n_parts, false, false, 0);
   if (direct) return IPLS_OK;                           // stream-ordered
   const hipMemcpyKind kind = out_kind == IPLS_DEV_TEXT ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   for (int i = 0; i < n_parts; ++i)
     HIP_TRY(h, hipMemcpyAsync((unsigned char*)out + offs[i], base + offs[i], (size_t)lens[i], kind, h->stream));
   if (out_kind == IPLS_HOST_TEXT) HIP_TRY(h, hipStreamSynchronize(h->stream));
   return IPLS_OK;
+}
+
+int64_t dev_send_many_segs(ipls_dev* h, const seg_ref* segs, int n_segs, int n_parts, const int* parts,
+                           int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
+                           const int64_t* offs, const int64_t* lens, int out_kind) {
+  return send_many_segs(h, segs, nullptr, n_segs, n_parts, parts, iteration, pid, origin, origin_len, out, offs, lens,
+                        out_kind);
+}
+int64_t dev_send_many_segs_diff(ipls_dev* h, const seg_ref* segs, const void* const* b_ptrs, int n_segs, int n_parts,
+                                const int* parts, int32_t iteration, int16_t pid, const uint8_t* origin,
+                                int32_t origin_len, void* out, const int64_t* offs, const int64_t* lens, int out_kind) {
+  if (n_segs > 0 && !b_ptrs) return fail(h, IPLS_E_INVAL, "null subtrahend list");
+  static const void* const none[1] = {nullptr};
+  return send_many_segs(h, segs, b_ptrs ? b_ptrs : none, n_segs, n_parts, parts, iteration, pid, origin, origin_len,
+                        out, offs, lens, out_kind);
 }
 
 // ---- saved-model files on the device (engine.hpp) ----

@@ -159,6 +159,15 @@ int64_t dev_send_many_segs(ipls_dev* h, const seg_ref* segs, int n_segs, int n_p
                            int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
                            const int64_t* offs, const int64_t* lens, int out_kind);
 
+// The difference calls (ipls_agg_*_segs_diff; seg_diff_kernels.hpp): segs is the minuend list and makes the plan;
+// b_ptrs[s] is the subtrahend array of segment s, of segs[s]'s length and format (not looked at when that is empty).
+// They share the twins' code: a twin is the same path with no subtrahend list.
+int dev_update_gradient_segs_diff(ipls_dev* h, const seg_ref* segs, const void* const* b_ptrs, int n_segs,
+                                  const int32_t* owned, int n_owned);
+int64_t dev_send_many_segs_diff(ipls_dev* h, const seg_ref* segs, const void* const* b_ptrs, int n_segs, int n_parts,
+                                const int* parts, int32_t iteration, int16_t pid, const uint8_t* origin,
+                                int32_t origin_len, void* out, const int64_t* offs, const int64_t* lens, int out_kind);
+
 // ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
 // One run of a file that an engine packs: `prefix` (framing), then engine
 // partition q's values of `target`, then `suffix` (a byte, or -1).

@@ -1408,9 +1408,12 @@ int segs_total(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const in
   return IPLS_OK;
 }
 
+// list: null for a plain segment list (the messages name the segment), else the name of the list of a difference
+// call ("minuend" / "subtrahend"; the messages name the segment and the list).
 int segs_check(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds, int n_segs,
-               std::vector<seg_ref>& out) {
+               std::vector<seg_ref>& out, const char* list = nullptr) {
   namespace sp = ipls::segplan;
+  const std::string of = list ? std::string(list) + " " : std::string();
   out.resize((size_t)n_segs);
   for (int s = 0; s < n_segs; ++s) {
     const int k = kinds[s];
@@ -1418,10 +1421,10 @@ int segs_check(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const in
                     : k == IPLS_DEV_BF16 ? sp::kBF16 : -1;
     if (fmt < 0) return ferr(H, IPLS_E_INVAL, "segment %d: kind %d is not DEV_F64 / DEV_F32 / DEV_F16 / DEV_BF16", s, k);
     if (ns[s] < 0) return ferr(H, IPLS_E_INVAL, "segment %d: negative length %lld", s, (long long)ns[s]);
-    if (ns[s] > 0 && !ptrs[s]) return ferr(H, IPLS_E_INVAL, "segment %d: null pointer", s);
+    if (ns[s] > 0 && !ptrs[s]) return ferr(H, IPLS_E_INVAL, "%ssegment %d: null pointer", of.c_str(), s);
     const int esz = sp::fmt_esz(fmt);
     if (ns[s] > 0 && ((uintptr_t)ptrs[s] & (uintptr_t)(esz - 1)))
-      return ferr(H, IPLS_E_INVAL, "segment %d: pointer not %d-byte aligned", s, esz);
+      return ferr(H, IPLS_E_INVAL, "%ssegment %d: pointer not %d-byte aligned", of.c_str(), s, esz);
     // an empty segment's pointer is never looked at again
     out[(size_t)s] = seg_ref{ns[s] > 0 ? ptrs[s] : nullptr, ns[s], fmt};
   }
@@ -1452,34 +1455,6 @@ int segs_reach(ipls_agg* H, int s, const std::vector<seg_ref>& segs, int64_t a, 
 
 }  // namespace
 
-int ipls_agg_update_gradient_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
-                                  int n_segs, const int32_t* owned, int n_owned) {
-  KeepDevice keep_device;
-  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
-  int64_t n = 0;
-  if (int rc = segs_total(H, ptrs, ns, kinds, n_segs, &n)) return rc;
-  if (int rc = segs_bounds(H, n)) return rc;
-  if (n_owned < 0 || (n_owned > 0 && !owned)) return ferr(H, IPLS_E_INVAL, "bad owned list");
-  for (int i = 0; i < n_owned; ++i)
-    if (!part_ok(H, owned[i])) return range_err(H, owned[i]);
-  std::vector<seg_ref> segs;
-  if (int rc = segs_check(H, ptrs, ns, kinds, n_segs, segs)) return rc;
-  if (n_owned == 0) return IPLS_OK;
-  std::vector<std::vector<int32_t>> per(H->S());
-  for (int i = 0; i < n_owned; ++i) per[H->owner[owned[i]]].push_back(owned[i] - H->lo[H->owner[owned[i]]]);
-  std::vector<int> ss;
-  for (int s = 0; s < H->S(); ++s)
-    if (!per[s].empty()) ss.push_back(s);
-  if (H->S() > 1)
-    for (int s : ss)
-      if (int rc = segs_reach(H, s, segs, H->off[H->lo[s]], H->off[H->lo[s + 1] - 1] + H->chunk, "gradient segment"))
-        return rc;
-  H->last_shard.store(ss.back(), std::memory_order_relaxed);
-  return par_shards(H, ss, [&](int s) {
-    return dev_update_gradient_segs(H->sh[s], segs.data(), n_segs, per[s].data(), (int)per[s].size());
-  });
-}
-
 int ipls_agg_get_partitions_segs(ipls_agg* H, void* const* ptrs, const int64_t* ns, const int32_t* kinds, int n_segs) {
   KeepDevice keep_device;
   if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
@@ -1500,14 +1475,64 @@ int ipls_agg_get_partitions_segs(ipls_agg* H, void* const* ptrs, const int64_t* 
   return par_shards(H, ss, [&](int s) { return dev_get_partitions_segs(H->sh[s], segs.data(), n_segs); });
 }
 
-int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
-                                     int n_segs, const int32_t* parts, int n_parts, int32_t iteration, int16_t pid,
-                                     const uint8_t* origin, int32_t origin_len, void* out, int64_t out_cap,
-                                     int out_kind, int64_t* lens, int64_t* offs) {
+// ---- UpdateGradient and SendGradients over a segment list, and over the difference of two ----
+// One body each for the plain call (diff false: b_ptrs is not looked at) and the difference call (two pointer
+// tables over one table of lengths and kinds): the same checks in the same order, the subtrahend list after the
+// minuend list wherever a list is looked at.
+namespace {
+// The subtrahend list of a difference call, checked after the minuend list: its pointers as the engines take them.
+int diff_check(ipls_agg* H, const void* const* b_ptrs, const int64_t* ns, const int32_t* kinds, int n_segs,
+               std::vector<seg_ref>& b_segs, std::vector<const void*>& b) {
+  if (int rc = segs_check(H, b_ptrs, ns, kinds, n_segs, b_segs, "subtrahend")) return rc;
+  b.assign((size_t)std::max(n_segs, 1), nullptr);
+  for (int s = 0; s < n_segs; ++s) b[(size_t)s] = b_segs[(size_t)s].ptr;
+  return IPLS_OK;
+}
+
+int update_gradient_segs(ipls_agg* H, bool diff, const void* const* a_ptrs, const void* const* b_ptrs,
+                         const int64_t* ns, const int32_t* kinds, int n_segs, const int32_t* owned, int n_owned) {
   KeepDevice keep_device;
   if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
   int64_t n = 0;
-  if (int rc = segs_total(H, ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (int rc = segs_total(H, a_ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (diff && n_segs > 0 && !b_ptrs) return ferr(H, IPLS_E_INVAL, "bad segment table: null subtrahend list");
+  if (int rc = segs_bounds(H, n)) return rc;
+  if (n_owned < 0 || (n_owned > 0 && !owned)) return ferr(H, IPLS_E_INVAL, "bad owned list");
+  for (int i = 0; i < n_owned; ++i)
+    if (!part_ok(H, owned[i])) return range_err(H, owned[i]);
+  std::vector<seg_ref> segs, b_segs;
+  std::vector<const void*> b;
+  if (int rc = segs_check(H, a_ptrs, ns, kinds, n_segs, segs, diff ? "minuend" : nullptr)) return rc;
+  if (diff)
+    if (int rc = diff_check(H, b_ptrs, ns, kinds, n_segs, b_segs, b)) return rc;
+  if (n_owned == 0) return IPLS_OK;
+  std::vector<std::vector<int32_t>> per(H->S());
+  for (int i = 0; i < n_owned; ++i) per[H->owner[owned[i]]].push_back(owned[i] - H->lo[H->owner[owned[i]]]);
+  std::vector<int> ss;
+  for (int s = 0; s < H->S(); ++s)
+    if (!per[s].empty()) ss.push_back(s);
+  if (H->S() > 1)
+    for (int s : ss) {
+      const int64_t lo = H->off[H->lo[s]], hi = H->off[H->lo[s + 1] - 1] + H->chunk;
+      if (int rc = segs_reach(H, s, segs, lo, hi, diff ? "minuend segment" : "gradient segment")) return rc;
+      if (int rc = segs_reach(H, s, b_segs, lo, hi, "subtrahend segment")) return rc;
+    }
+  H->last_shard.store(ss.back(), std::memory_order_relaxed);
+  return par_shards(H, ss, [&](int s) {
+    if (!diff) return dev_update_gradient_segs(H->sh[s], segs.data(), n_segs, per[s].data(), (int)per[s].size());
+    return dev_update_gradient_segs_diff(H->sh[s], segs.data(), b.data(), n_segs, per[s].data(), (int)per[s].size());
+  });
+}
+
+int64_t send_gradients_segs(ipls_agg* H, bool diff, const void* const* a_ptrs, const void* const* b_ptrs,
+                            const int64_t* ns, const int32_t* kinds, int n_segs, const int32_t* parts, int n_parts,
+                            int32_t iteration, int16_t pid, const uint8_t* origin, int32_t origin_len, void* out,
+                            int64_t out_cap, int out_kind, int64_t* lens, int64_t* offs) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  int64_t n = 0;
+  if (int rc = segs_total(H, a_ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (diff && n_segs > 0 && !b_ptrs) return ferr(H, IPLS_E_INVAL, "bad segment table: null subtrahend list");
   if (n_parts < 0 || (n_parts > 0 && !parts)) return ferr(H, IPLS_E_INVAL, "bad partition list");
   if (origin_len < 0 || (out && origin_len > 0 && !origin)) return ferr(H, IPLS_E_INVAL, "bad origin");
   if (out_kind != IPLS_HOST_TEXT && out_kind != IPLS_DEV_TEXT) return ferr(H, IPLS_E_INVAL, "out_kind HOST_TEXT/DEV_TEXT");
@@ -1524,8 +1549,11 @@ int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const
   if (!out || n_parts == 0) return total;
   if (int rc = segs_bounds(H, n)) return rc;
   if (out_cap < total) return ferr(H, IPLS_E_RANGE, "gradient texts need %lld bytes", (long long)total);
-  std::vector<seg_ref> segs;
-  if (int rc = segs_check(H, ptrs, ns, kinds, n_segs, segs)) return rc;
+  std::vector<seg_ref> segs, b_segs;
+  std::vector<const void*> b;
+  if (int rc = segs_check(H, a_ptrs, ns, kinds, n_segs, segs, diff ? "minuend" : nullptr)) return rc;
+  if (diff)
+    if (int rc = diff_check(H, b_ptrs, ns, kinds, n_segs, b_segs, b)) return rc;
   // group by owner shard; each shard encodes its texts in one launch
   std::vector<std::vector<int>> idx(H->S());
   for (int i = 0; i < n_parts; ++i) idx[H->owner[parts[i]]].push_back(i);
@@ -1534,8 +1562,9 @@ int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const
       if (idx[s].empty()) continue;
       if (out_kind == IPLS_DEV_TEXT)
         if (int rc = check_reach(H, s, out, "text buffer")) return rc;
-      if (int rc = segs_reach(H, s, segs, H->off[H->lo[s]], H->off[H->lo[s + 1] - 1] + H->chunk, "gradient segment"))
-        return rc;
+      const int64_t lo = H->off[H->lo[s]], hi = H->off[H->lo[s + 1] - 1] + H->chunk;
+      if (int rc = segs_reach(H, s, segs, lo, hi, diff ? "minuend segment" : "gradient segment")) return rc;
+      if (int rc = segs_reach(H, s, b_segs, lo, hi, "subtrahend segment")) return rc;
     }
   for (int s = 0; s < H->S(); ++s) {
     if (idx[s].empty()) continue;
@@ -1547,12 +1576,41 @@ int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const
       ll.push_back(L[i]);
     }
     H->last_shard = s;
-    if (int64_t rc = dev_send_many_segs(H->sh[s], segs.data(), n_segs, (int)lp.size(), lp.data(), iteration, pid,
-                                        origin, origin_len, out, oo.data(), ll.data(), out_kind);
-        rc < 0)
-      return fwd(H, s, (int)rc);
+    const int64_t rc =
+        diff ? dev_send_many_segs_diff(H->sh[s], segs.data(), b.data(), n_segs, (int)lp.size(), lp.data(), iteration,
+                                       pid, origin, origin_len, out, oo.data(), ll.data(), out_kind)
+             : dev_send_many_segs(H->sh[s], segs.data(), n_segs, (int)lp.size(), lp.data(), iteration, pid, origin,
+                                  origin_len, out, oo.data(), ll.data(), out_kind);
+    if (rc < 0) return fwd(H, s, (int)rc);
   }
   return total;
+}
+
+}  // namespace
+
+int ipls_agg_update_gradient_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
+                                  int n_segs, const int32_t* owned, int n_owned) {
+  return update_gradient_segs(H, false, ptrs, nullptr, ns, kinds, n_segs, owned, n_owned);
+}
+int ipls_agg_update_gradient_segs_diff(ipls_agg* H, const void* const* a_ptrs, const void* const* b_ptrs,
+                                       const int64_t* ns, const int32_t* kinds, int n_segs, const int32_t* owned,
+                                       int n_owned) {
+  return update_gradient_segs(H, true, a_ptrs, b_ptrs, ns, kinds, n_segs, owned, n_owned);
+}
+int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
+                                     int n_segs, const int32_t* parts, int n_parts, int32_t iteration, int16_t pid,
+                                     const uint8_t* origin, int32_t origin_len, void* out, int64_t out_cap,
+                                     int out_kind, int64_t* lens, int64_t* offs) {
+  return send_gradients_segs(H, false, ptrs, nullptr, ns, kinds, n_segs, parts, n_parts, iteration, pid, origin,
+                             origin_len, out, out_cap, out_kind, lens, offs);
+}
+int64_t ipls_agg_send_gradients_segs_diff(ipls_agg* H, const void* const* a_ptrs, const void* const* b_ptrs,
+                                          const int64_t* ns, const int32_t* kinds, int n_segs, const int32_t* parts,
+                                          int n_parts, int32_t iteration, int16_t pid, const uint8_t* origin,
+                                          int32_t origin_len, void* out, int64_t out_cap, int out_kind, int64_t* lens,
+                                          int64_t* offs) {
+  return send_gradients_segs(H, true, a_ptrs, b_ptrs, ns, kinds, n_segs, parts, n_parts, iteration, pid, origin,
+                             origin_len, out, out_cap, out_kind, lens, offs);
 }
 
 // ---- saved-model files (javaser.hpp) ----

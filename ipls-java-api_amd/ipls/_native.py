@@ -36,6 +36,8 @@ KERNEL_UPDATE_FLAT = 11                      # k_update_flat: one whole streamed
 KERNEL_ENCODE_FLAT = 12                      # k_b64url_encode_flat: a flat gradient's partitions as texts (send_gradients)
 # the segment-list calls (k_update_segs, k_divide_segs, k_b64url_encode_segs): a list of tensors in or out
 KERNEL_UPDATE_SEGS, KERNEL_DIVIDE_SEGS, KERNEL_ENCODE_SEGS = 13, 14, 15
+# the difference-list calls (k_update_segs_diff, k_b64url_encode_segs_diff): minuend list minus subtrahend list
+KERNEL_UPDATE_SEGS_DIFF, KERNEL_ENCODE_SEGS_DIFF = 16, 17
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -171,6 +173,10 @@ SIGNATURES = {
     "ipls_agg_send_gradients_segs": (_i64, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp, _i64, _i,
                                             _vp, _vp]),
     "ipls_agg_get_partitions_segs": (_i, [_vp, _vp, _vp, _vp, _i]),
+    # difference lists: a_ptrs (minuend) and b_ptrs (subtrahend) over one ns / kinds table
+    "ipls_agg_update_gradient_segs_diff": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i]),
+    "ipls_agg_send_gradients_segs_diff": (_i64, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp,
+                                                 _i64, _i, _vp, _vp]),
     "ipls_agg_last_launch": (_i, [_vp, _P(LaunchInfo)]),
     # saved-model files; the host-only encoders take typed first pointers (NULL is a valid empty input)
     "ipls_saved_parse": (_i64, [_vp, _i64, _P(_i32), _P(_i64), _P(_i64), _i64]),

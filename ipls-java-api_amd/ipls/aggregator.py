@@ -140,6 +140,46 @@ class Segments:
         return self._ptrs, self._ns, self._kinds, self.n_segs
 
 
+class Difference:
+    """The trainer's update as the difference of two lists of device tensors,
+    ``minuend[s] - subtrahend[s]`` element by element in each pair's own dtype
+    (what ``torch.sub`` gives), only the result widened -- the reference's
+    ``GetDiff(model.params(), Dumm)`` = ``Dumm.sub(params)`` (Model.java:413:
+    ``Difference(received_model, trained_params)``) without the third list a
+    ``torch._foreach_sub`` would make (include/ipls_agg.h, the ``_segs_diff``
+    calls).  Each argument is a ``Segments`` or a list / tuple of CUDA
+    tensors; a single tensor counts as a list of one, so two flat tensors are
+    a one-segment difference.  The pairs must agree in number, ``numel()`` and
+    dtype, else a ValueError naming the tensor, before any library call.  The
+    object keeps both lists alive and can be passed again every step to
+    ``UpdateGradient`` and ``SendGradients``; ``n`` is the number of values,
+    ``n_segs`` the number of pairs.  The lists may alias."""
+
+    def __init__(self, minuend, subtrahend):
+        a, b = self._list(minuend), self._list(subtrahend)
+        if a.n_segs != b.n_segs:
+            raise ValueError(f"minuend has {a.n_segs} tensors, subtrahend {b.n_segs}")
+        for i, (x, y) in enumerate(zip(a.tensors, b.tensors)):
+            if x.numel() != y.numel():
+                raise ValueError(f"tensor {i}: minuend has {x.numel()} elements, subtrahend {y.numel()}")
+            if x.dtype != y.dtype:
+                raise ValueError(f"tensor {i}: minuend dtype {x.dtype}, subtrahend dtype {y.dtype}")
+        self.minuend, self.subtrahend = a, b
+        self.n, self.n_segs = a.n, a.n_segs
+
+    @staticmethod
+    def _list(x):
+        if isinstance(x, Segments):
+            return x
+        return Segments.from_tensors(x if isinstance(x, (list, tuple)) else [x])
+
+    @property
+    def tables(self):
+        """(a_ptrs, b_ptrs, ns, kinds, n_segs) as the C calls take them."""
+        a_ptrs, ns, kinds, k = self.minuend.tables
+        return a_ptrs, self.subtrahend.tables[0], ns, kinds, k
+
+
 def _segments(x):
     """x as a Segments when it is one, or a list / tuple of CUDA tensors (wrapped on the fly); else None."""
     if isinstance(x, Segments):
@@ -256,6 +296,8 @@ def _host_operand(x, big_endian: bool, f32: bool = False):
 
 
 def _operand(x, big_endian: bool = False, f32: bool = False):
+    if isinstance(x, Difference):
+        raise TypeError("a Difference is an operand of UpdateGradient and SendGradients only")
     if isinstance(x, DeviceBuffer):
         return x.ptr, x.n, x.kind, x
     return _host_operand(x, big_endian, f32)
@@ -412,6 +454,10 @@ class Aggregator:
         tensors lie: no ``torch.cat``, no cast pass."""
         owned = np.ascontiguousarray(np.asarray(list(auth_list), dtype=np.int32))
         if gradients is None:
+            return
+        if isinstance(gradients, Difference):   # minuend - subtrahend, both read where they lie (k_update_segs_diff)
+            self._chk(self._lib.ipls_agg_update_gradient_segs_diff(self._h, *gradients.tables, owned.ctypes.data,
+                                                                   len(owned)))
             return
         segs = _segments(gradients)
         if segs is not None:   # a list of device tensors, read where they lie (k_update_segs)
@@ -947,6 +993,8 @@ class Aggregator:
         gets every tensor written in its own dtype by those same rules, with
         no flat model and no copy-out in between."""
         n = self.flat_size
+        if isinstance(out, Difference):
+            raise TypeError("a Difference is an operand of UpdateGradient and SendGradients only, not an output")
         if isinstance(out, Segments):   # straight into the model's tensors, each in its own dtype (k_divide_segs)
             self._chk(self._lib.ipls_agg_get_partitions_segs(self._h, *out.tables))
             return out
@@ -1129,8 +1177,9 @@ class Aggregator:
         parts = np.ascontiguousarray(list(partitions), dtype=np.int32)
         o = np.frombuffer(bytes(origin), dtype=np.uint8)
         op = o.ctypes.data if o.size else None
-        segs = _segments(gradients)
-        if segs is not None or gradients is None:
+        diff = gradients if isinstance(gradients, Difference) else None
+        segs = None if diff is not None else _segments(gradients)
+        if diff is not None or segs is not None or gradients is None:
             ptr, ng, kind, keep = None, 0, N.HOST_F64, None
         else:
             if getattr(gradients, "is_cuda", False):   # a GPU torch tensor: read where it lies
@@ -1141,6 +1190,9 @@ class Aggregator:
         offs = np.zeros(max(1, n), dtype=np.int64)
 
         def call(dst, cap, dst_kind, le=None, of=None):
+            if diff is not None:   # minuend - subtrahend, both read where they lie (k_b64url_encode_segs_diff)
+                return self._chk(self._lib.ipls_agg_send_gradients_segs_diff(
+                    self._h, *diff.tables, parts.ctypes.data, n, iteration, pid, op, o.size, dst, cap, dst_kind, le, of))
             if segs is not None:   # a list of device tensors, read where they lie (k_b64url_encode_segs)
                 return self._chk(self._lib.ipls_agg_send_gradients_segs(
                     self._h, *segs.tables, parts.ctypes.data, n, iteration, pid, op, o.size, dst, cap, dst_kind, le, of))
