@@ -914,6 +914,56 @@ int64_t ipls_agg_send_gradients_segs_diff(ipls_agg *h, const void *const *a_ptrs
                                           const uint8_t *origin, int32_t origin_len,
                                           void *out, int64_t out_cap, int out_kind, int64_t *lens, int64_t *offs);
 
+/* ---- K trainers' lists folded in one call ----
+ *
+ * The reference's documented experiment is many trainers against one machine
+ * (Model.java:98-105; remote_fit and the Computational_Server, Model.java:134-
+ * 140, 407-410, exist to make that bearable).  On one GPU that is K models of
+ * one architecture side by side, all trained from the same received model.
+ * A PEER LIST is n_peers segment lists over one ns / kinds table, lengths and
+ * kinds equal by construction: t_ptrs[k * n_segs + s] is peer k's array of
+ * segment s (peer-major).  Peer k's flat value f = start_s + e is
+ *   m_ptrs == NULL   (double) t_k[s][e]: K plain lists;
+ *   m_ptrs != NULL   (double) sub_kind(m[s][e], t_k[s][e]): the one shared
+ *                    minuend list (the received model) minus trainer k's
+ *                    parameters, the subtraction made in the segment's own
+ *                    format exactly as the _segs_diff calls define it.
+ * The accumulators, their logically-zero states and the count slots end with
+ * the bits of calling ipls_agg_update_gradient_segs(t_k) -- or
+ * ipls_agg_update_gradient_segs_diff(a_ptrs = m_ptrs, b_ptrs = t_k) -- once
+ * per peer, for k = 0 .. n_peers - 1 in that order, with the same `owned`:
+ * a partition owned once gets (((start + v_0) + v_1) + ..) + v_{K-1}, start =
+ * +0.0 where the accumulator is logically zero; its count slot is added 1.0
+ * K times, one after another; the tail above it +0.0 K times (a -0.0 there
+ * becomes +0.0).  Nothing on the peer axis is reassociated.  A partition
+ * listed r times in `owned` gets each peer's value added r times in a row
+ * before the next peer's (the bits of K calls whose repeat levels run inside
+ * each call).  Queued arrivals of a shard are folded before anything of this
+ * call, as by a single ipls_agg_update_gradient.  The whole call is one
+ * ordered unit: one hold of each involved shard's lock, one launch per shard,
+ * all or nothing -- every check runs before the first launch on any shard, in
+ * the twins' order: geometry (every partition bounded: IPLS_E_RANGE), `owned`,
+ * then the lists, the minuend first, then peers 0 .. K-1.
+ * n_peers < 1, n_peers > IPLS_SEG_PEERS_MAX and a NULL t_ptrs are
+ * IPLS_E_INVAL; a NULL or misaligned pointer of a non-empty segment is
+ * IPLS_E_INVAL, the message naming the segment and the list ("minuend" /
+ * "peer k"); kinds and lengths as for the _segs calls.  On a handle over
+ * several GPUs every array of ANY list that a shard touches must be memory its
+ * device can reach (IPLS_E_DEVICE before anything is written).  n_segs == 0 is
+ * the vector of no values, K times.  The lists may alias each other, the
+ * minuend included.  n_peers == 1 is this call's own kernel too, not the
+ * twin's (ipls_agg_last_launch says IPLS_KERNEL_UPDATE_SEGS_PEERS).
+ * What does not exist: per-peer minuends, pairs of different kinds, host
+ * lists, a send twin (each simulated peer's texts carry its own origin), JNI
+ * and C++ mirrors, and a cache of plans between calls. */
+#define IPLS_SEG_PEERS_MAX 1024
+int ipls_agg_update_gradient_segs_peers(ipls_agg *h,
+                                        const void *const *m_ptrs,   /* n_segs minuend pointers, or NULL */
+                                        const void *const *t_ptrs,   /* n_peers * n_segs, peer-major */
+                                        int n_peers,
+                                        const int64_t *ns, const int32_t *kinds, int n_segs,
+                                        const int32_t *owned, int n_owned);
+
 /* ---- observability ----
  * What the last fold launch of a handle (of p's shard for multi-GPU handles:
  * the shard of the last call) ran: the kernel, the tile shape chosen by the
@@ -963,8 +1013,10 @@ enum {
                                         seqf 1 when at least one lane had its four values in one segment */
     IPLS_KERNEL_UPDATE_SEGS_DIFF = 16, /* k_update_segs_diff (update_gradient_segs_diff): every field as for
                                         IPLS_KERNEL_UPDATE_SEGS */
-    IPLS_KERNEL_ENCODE_SEGS_DIFF = 17  /* k_b64url_encode_segs_diff (send_gradients_segs_diff): every field as for
+    IPLS_KERNEL_ENCODE_SEGS_DIFF = 17, /* k_b64url_encode_segs_diff (send_gradients_segs_diff): every field as for
                                         IPLS_KERNEL_ENCODE_SEGS */
+    IPLS_KERNEL_UPDATE_SEGS_PEERS = 18 /* k_update_segs_peers (update_gradient_segs_peers): one launch per shard
+                                        whatever `owned` repeats; every field as for IPLS_KERNEL_UPDATE_SEGS */
 };
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2

@@ -37,6 +37,7 @@
 #include "ipls_kernels.hpp"
 #include "seg_kernels.hpp"
 #include "seg_diff_kernels.hpp"
+#include "seg_peers_kernels.hpp"
 #include "javaser.hpp"
 #include "engine.hpp"
 #include "operand.hpp"
@@ -3346,6 +3347,66 @@ int dev_update_gradient_segs_diff(ipls_dev* h, const seg_ref* segs, const void* 
   if (n_segs > 0 && !b_ptrs) return fail(h, IPLS_E_INVAL, "null subtrahend list");
   static const void* const none[1] = {nullptr};
   return update_segs(h, segs, b_ptrs ? b_ptrs : none, n_segs, owned, n_owned);
+}
+
+// The peer-list call: K lists in one launch.  The plan is made over `owned` without its repeats (so it has one
+// launch); how often a partition stood in `owned` goes into its job, and the kernel adds every peer's value that
+// often in a row -- the bits of K twin calls whose repeat levels run inside each call.
+int dev_update_gradient_segs_peers(ipls_dev* h, const seg_ref* segs, bool diff, const void* const* t_ptrs, int n_peers,
+                                   int n_segs, const int32_t* owned, int n_owned) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  IPLS_LOCK(h);
+  if (n_peers < 1 || !t_ptrs) return fail(h, IPLS_E_INVAL, "bad peer list");
+  const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
+  std::vector<int32_t> uniq;                          // owned without repeats, in order of first appearance
+  std::vector<int32_t> mult((size_t)h->P, 0);
+  bool listed = n_owned >= 0 && (n_owned == 0 || owned);
+  for (int i = 0; listed && i < n_owned; ++i) {
+    listed = owned[i] >= 0 && owned[i] < h->P;
+    if (listed && mult[(size_t)owned[i]]++ == 0) uniq.push_back(owned[i]);
+  }
+  // a list the plan refuses goes to it as it came
+  const segplan::Plan pl = listed ? segplan::plan_update(seg_geometry(h), tab.data(), n_segs, uniq.data(),
+                                                         (int)uniq.size(), kSegTile)
+                                  : segplan::plan_update(seg_geometry(h), tab.data(), n_segs, owned, n_owned, kSegTile);
+  if (int rc = seg_plan_rc(h, pl)) return rc;
+  if (n_owned == 0) return IPLS_OK;
+  HIP_TRY(h, dev_use(h->device));
+  const segplan::Launch& l = pl.launches[0];          // no repeats: one launch
+  const std::vector<SegPiece> pieces = seg_pieces(pl, segs);
+  std::vector<const void*> psrc(pieces.size() * (size_t)n_peers);
+  for (size_t k = 0; k < pieces.size(); ++k) {
+    const segplan::Piece& p = pl.pieces[k];
+    const int64_t at = p.src * segplan::fmt_esz(segs[p.seg].fmt);
+    for (int q = 0; q < n_peers; ++q)
+      psrc[k * (size_t)n_peers + (size_t)q] = (const char*)t_ptrs[(size_t)q * (size_t)n_segs + (size_t)p.seg] + at;
+  }
+  std::vector<SegPeersJob> jobs(l.jobs.size());
+  bool all_zero = true;
+  for (size_t j = 0; j < jobs.size(); ++j) {
+    const int q = l.jobs[j].q;
+    jobs[j] = SegPeersJob{(unsigned long long*)(h->arena + h->agg_off[q]), l.jobs[j].ncopy, l.jobs[j].L,
+                          h->agg_zero[q] ? 1 : 0, mult[(size_t)q]};
+    all_zero = all_zero && h->agg_zero[q];
+  }
+  TablePack pack;
+  const size_t at_items = pack.add(l.items.data(), l.items.size());
+  const size_t at_jobs = pack.add(jobs.data(), jobs.size());
+  const size_t at_pieces = pack.add(pieces.data(), pieces.size());
+  const size_t at_psrc = pack.add(psrc.data(), psrc.size());
+  void* d = nullptr;
+  if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &d)) return rc;
+  const char* dt = (const char*)d;
+  with_bool(diff, [&](auto df) {
+    hipLaunchKernelGGL((k_update_segs_peers<decltype(df)::value>), dim3((unsigned)l.items.size()), dim3(kBlock), 0,
+                       h->stream, (const segplan::Item*)(dt + at_items), (const SegPeersJob*)(dt + at_jobs),
+                       (const SegPiece*)(dt + at_pieces), (const void* const*)(dt + at_psrc), n_peers);
+  });
+  HIP_TRY(h, hipGetLastError());
+  for (const segplan::Job& j : l.jobs) h->agg_zero[j.q] = 0;
+  h->last_launch = launch_info(IPLS_KERNEL_UPDATE_SEGS_PEERS, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
+                               (int64_t)l.items.size(), false, false, all_zero ? kZero : kAccum);
+  return IPLS_OK;
 }
 
 int dev_get_partitions_segs(ipls_dev* h, const seg_ref* segs, int n_segs) {

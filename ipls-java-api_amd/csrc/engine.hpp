@@ -168,6 +168,13 @@ int64_t dev_send_many_segs_diff(ipls_dev* h, const seg_ref* segs, const void* co
                                 const int* parts, int32_t iteration, int16_t pid, const uint8_t* origin,
                                 int32_t origin_len, void* out, const int64_t* offs, const int64_t* lens, int out_kind);
 
+// The peer-list call (ipls_agg_update_gradient_segs_peers; seg_peers_kernels.hpp): n_peers lists over one table.
+// segs makes the plan: the shared minuend list (diff), else peer 0's list.  t_ptrs[k * n_segs + s] is peer k's
+// array of segment s, of segs[s]'s length and format (not looked at when that is empty).  One launch: a partition
+// repeated in `owned` becomes a multiplicity of its job.
+int dev_update_gradient_segs_peers(ipls_dev* h, const seg_ref* segs, bool diff, const void* const* t_ptrs, int n_peers,
+                                   int n_segs, const int32_t* owned, int n_owned);
+
 // ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
 // One run of a file that an engine packs: `prefix` (framing), then engine
 // partition q's values of `target`, then `suffix` (a byte, or -1).

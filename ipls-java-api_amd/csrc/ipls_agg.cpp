@@ -1597,6 +1597,55 @@ int ipls_agg_update_gradient_segs_diff(ipls_agg* H, const void* const* a_ptrs, c
                                        int n_owned) {
   return update_gradient_segs(H, true, a_ptrs, b_ptrs, ns, kinds, n_segs, owned, n_owned);
 }
+// K lists over one table, folded as one unit: the twins' checks in the twins' order (geometry, owned, then the
+// lists -- the minuend first, then peers 0 .. K-1), all before the first launch on any shard.
+int ipls_agg_update_gradient_segs_peers(ipls_agg* H, const void* const* m_ptrs, const void* const* t_ptrs, int n_peers,
+                                        const int64_t* ns, const int32_t* kinds, int n_segs, const int32_t* owned,
+                                        int n_owned) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (n_peers < 1 || n_peers > IPLS_SEG_PEERS_MAX)
+    return ferr(H, IPLS_E_INVAL, "n_peers %d outside [1, %d]", n_peers, IPLS_SEG_PEERS_MAX);
+  if (!t_ptrs) return ferr(H, IPLS_E_INVAL, "bad segment table: null peer list");
+  int64_t n = 0;
+  if (int rc = segs_total(H, t_ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (int rc = segs_bounds(H, n)) return rc;
+  if (n_owned < 0 || (n_owned > 0 && !owned)) return ferr(H, IPLS_E_INVAL, "bad owned list");
+  for (int i = 0; i < n_owned; ++i)
+    if (!part_ok(H, owned[i])) return range_err(H, owned[i]);
+  const bool diff = m_ptrs != nullptr;
+  std::vector<seg_ref> m_segs;
+  std::vector<std::vector<seg_ref>> t_segs((size_t)n_peers);
+  if (diff)
+    if (int rc = segs_check(H, m_ptrs, ns, kinds, n_segs, m_segs, "minuend")) return rc;
+  for (int k = 0; k < n_peers; ++k) {
+    const std::string name = "peer " + std::to_string(k);
+    if (int rc = segs_check(H, t_ptrs + (size_t)k * (size_t)n_segs, ns, kinds, n_segs, t_segs[(size_t)k], name.c_str()))
+      return rc;
+  }
+  if (n_owned == 0) return IPLS_OK;
+  std::vector<const void*> t((size_t)n_peers * (size_t)n_segs + 1, nullptr);   // an empty segment's pointer is null
+  for (int k = 0; k < n_peers; ++k)
+    for (int s = 0; s < n_segs; ++s) t[(size_t)k * (size_t)n_segs + (size_t)s] = t_segs[(size_t)k][(size_t)s].ptr;
+  const std::vector<seg_ref>& plan = diff ? m_segs : t_segs[0];
+  std::vector<std::vector<int32_t>> per(H->S());
+  for (int i = 0; i < n_owned; ++i) per[H->owner[owned[i]]].push_back(owned[i] - H->lo[H->owner[owned[i]]]);
+  std::vector<int> ss;
+  for (int s = 0; s < H->S(); ++s)
+    if (!per[s].empty()) ss.push_back(s);
+  if (H->S() > 1)
+    for (int s : ss) {
+      const int64_t lo = H->off[H->lo[s]], hi = H->off[H->lo[s + 1] - 1] + H->chunk;
+      if (int rc = segs_reach(H, s, m_segs, lo, hi, "minuend segment")) return rc;
+      for (int k = 0; k < n_peers; ++k)
+        if (int rc = segs_reach(H, s, t_segs[(size_t)k], lo, hi, "peer segment")) return rc;
+    }
+  H->last_shard.store(ss.back(), std::memory_order_relaxed);
+  return par_shards(H, ss, [&](int s) {
+    return dev_update_gradient_segs_peers(H->sh[s], plan.data(), diff, t.data(), n_peers, n_segs, per[s].data(),
+                                          (int)per[s].size());
+  });
+}
 int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
                                      int n_segs, const int32_t* parts, int n_parts, int32_t iteration, int16_t pid,
                                      const uint8_t* origin, int32_t origin_len, void* out, int64_t out_cap,

@@ -38,6 +38,9 @@ KERNEL_ENCODE_FLAT = 12                      # k_b64url_encode_flat: a flat grad
 KERNEL_UPDATE_SEGS, KERNEL_DIVIDE_SEGS, KERNEL_ENCODE_SEGS = 13, 14, 15
 # the difference-list calls (k_update_segs_diff, k_b64url_encode_segs_diff): minuend list minus subtrahend list
 KERNEL_UPDATE_SEGS_DIFF, KERNEL_ENCODE_SEGS_DIFF = 16, 17
+# the peer-list call (k_update_segs_peers): K lists over one table, folded in one launch
+KERNEL_UPDATE_SEGS_PEERS = 18
+SEG_PEERS_MAX = 1024
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -175,6 +178,7 @@ SIGNATURES = {
     "ipls_agg_get_partitions_segs": (_i, [_vp, _vp, _vp, _vp, _i]),
     # difference lists: a_ptrs (minuend) and b_ptrs (subtrahend) over one ns / kinds table
     "ipls_agg_update_gradient_segs_diff": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i]),
+    "ipls_agg_update_gradient_segs_peers": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "ipls_agg_send_gradients_segs_diff": (_i64, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp,
                                                  _i64, _i, _vp, _vp]),
     "ipls_agg_last_launch": (_i, [_vp, _P(LaunchInfo)]),

@@ -180,6 +180,50 @@ class Difference:
         return a_ptrs, self.subtrahend.tables[0], ns, kinds, k
 
 
+class PeerUpdates:
+    """The updates of K trainers of one architecture, folded by ONE
+    ``UpdateGradient`` call in peer order (include/ipls_agg.h,
+    ``ipls_agg_update_gradient_segs_peers``; k_update_segs_peers): the
+    accumulators end with the bits of K calls, one per peer, each with the
+    same ``auth_list``.  ``trained_lists`` holds one list per peer, each a
+    ``Segments``, a list / tuple of CUDA tensors or a single tensor.  With
+    ``received`` (the model every trainer started from, the same forms) peer
+    k's update is ``Difference(received, trained_lists[k])``, the received
+    model read once; without it the lists are the updates themselves.  Every
+    list must agree with peer 0's (and with ``received``) in number of
+    tensors, ``numel()`` and dtype, else a ValueError naming the peer and the
+    tensor, before any library call.  The object keeps every tensor alive and
+    can be passed again every step; ``n`` is the number of values,
+    ``n_segs`` the number of tensors per list, ``n_peers`` the number of
+    lists.  The lists may alias."""
+
+    def __init__(self, trained_lists, received=None):
+        peers = [Difference._list(x) for x in trained_lists]
+        if not 1 <= len(peers) <= N.SEG_PEERS_MAX:
+            raise ValueError(f"need 1 to {N.SEG_PEERS_MAX} peers, not {len(peers)}")
+        rec = None if received is None else Difference._list(received)
+        first = peers[0]
+        for name, x in ([("received", rec)] if rec is not None else []) + [(f"peer {k}", p) for k, p in
+                                                                           enumerate(peers[1:], 1)]:
+            if x.n_segs != first.n_segs:
+                raise ValueError(f"{name} has {x.n_segs} tensors, peer 0 has {first.n_segs}")
+            for i, (a, b) in enumerate(zip(first.tensors, x.tensors)):
+                if a.numel() != b.numel():
+                    raise ValueError(f"{name}, tensor {i}: {b.numel()} elements, peer 0 has {a.numel()}")
+                if a.dtype != b.dtype:
+                    raise ValueError(f"{name}, tensor {i}: dtype {b.dtype}, peer 0 has {a.dtype}")
+        self.peers, self.received = tuple(peers), rec
+        self.n, self.n_segs, self.n_peers = first.n, first.n_segs, len(peers)
+        k = self.n_segs
+        self._t_ptrs = (ctypes.c_void_p * max(k * self.n_peers, 1))(*[p.tables[0][s] for p in peers for s in range(k)])
+
+    @property
+    def tables(self):
+        """(m_ptrs or None, t_ptrs, n_peers, ns, kinds, n_segs) as the C call takes them."""
+        _, ns, kinds, k = self.peers[0].tables
+        return (None if self.received is None else self.received.tables[0]), self._t_ptrs, self.n_peers, ns, kinds, k
+
+
 def _segments(x):
     """x as a Segments when it is one, or a list / tuple of CUDA tensors (wrapped on the fly); else None."""
     if isinstance(x, Segments):
@@ -298,6 +342,8 @@ def _host_operand(x, big_endian: bool, f32: bool = False):
 def _operand(x, big_endian: bool = False, f32: bool = False):
     if isinstance(x, Difference):
         raise TypeError("a Difference is an operand of UpdateGradient and SendGradients only")
+    if isinstance(x, PeerUpdates):
+        raise TypeError("a PeerUpdates is an operand of UpdateGradient only")
     if isinstance(x, DeviceBuffer):
         return x.ptr, x.n, x.kind, x
     return _host_operand(x, big_endian, f32)
@@ -458,6 +504,10 @@ class Aggregator:
         if isinstance(gradients, Difference):   # minuend - subtrahend, both read where they lie (k_update_segs_diff)
             self._chk(self._lib.ipls_agg_update_gradient_segs_diff(self._h, *gradients.tables, owned.ctypes.data,
                                                                    len(owned)))
+            return
+        if isinstance(gradients, PeerUpdates):   # K trainers' lists in peer order, one launch (k_update_segs_peers)
+            self._chk(self._lib.ipls_agg_update_gradient_segs_peers(self._h, *gradients.tables, owned.ctypes.data,
+                                                                    len(owned)))
             return
         segs = _segments(gradients)
         if segs is not None:   # a list of device tensors, read where they lie (k_update_segs)
@@ -995,6 +1045,8 @@ class Aggregator:
         n = self.flat_size
         if isinstance(out, Difference):
             raise TypeError("a Difference is an operand of UpdateGradient and SendGradients only, not an output")
+        if isinstance(out, PeerUpdates):
+            raise TypeError("a PeerUpdates is an operand of UpdateGradient only, not an output")
         if isinstance(out, Segments):   # straight into the model's tensors, each in its own dtype (k_divide_segs)
             self._chk(self._lib.ipls_agg_get_partitions_segs(self._h, *out.tables))
             return out
