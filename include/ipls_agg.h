@@ -964,6 +964,44 @@ int ipls_agg_update_gradient_segs_peers(ipls_agg *h,
                                         const int64_t *ns, const int32_t *kinds, int n_segs,
                                         const int32_t *owned, int n_owned);
 
+/* ---- GetPartitions into K trainers' lists in one call ----
+ *
+ * The way back out of the many-trainers round: after it every one of the K
+ * trainers must hold the new model in its own parameter arrays, and so must
+ * the shared received model (the minuend of the next round's _segs_peers
+ * call).  An OUTPUT COPY LIST is n_lists segment lists over one ns / kinds
+ * table, lengths and kinds equal by construction: o_ptrs[k * n_segs + s] is
+ * list k's array of segment s (list-major), the device of the peer list.
+ * For every k, element f of list k ends with the bits that
+ * ipls_agg_get_partitions_segs writes when given list k alone: doubles stored
+ * as they are, F32 one rounding of the IEEE double quotient, F16 / BF16 the
+ * two-step rule, zero-count passthrough, secure mode's 1e12 * cnt divisor,
+ * values beyond the model size left unwritten, zero-length segments holding
+ * nothing (their pointers are not looked at).  W and the count slots are read
+ * once and the division is made once.  The whole call is one ordered unit: one
+ * hold of each involved shard's lock -- every list receives the same W,
+ * whatever another thread's aggregate or cache_partition does meanwhile --
+ * and one launch per shard, all or nothing: every check runs before the first
+ * launch on any shard, in the twin's order: the table, n < the flat size
+ * (IPLS_E_RANGE), then lists 0 .. n_lists - 1 (a NULL or misaligned pointer of
+ * a non-empty segment is IPLS_E_INVAL, the message naming the segment and
+ * "list k"; kinds and lengths as for the _segs calls), and on a handle over
+ * several GPUs every array of EVERY list that a shard touches must be memory
+ * its device can reach (IPLS_E_DEVICE).  A refusal writes nothing to any list.
+ * n_lists < 1, n_lists > IPLS_SEG_COPIES_MAX and a NULL o_ptrs with n_segs > 0
+ * are IPLS_E_INVAL.  Lists that overlap each other are the caller's problem,
+ * as overlapping output segments are for the twin.  n_lists == 1 is this
+ * call's own kernel too, not the twin's (ipls_agg_last_launch says
+ * IPLS_KERNEL_DIVIDE_SEGS_COPIES).  Stream ordering, and on a handle over
+ * several GPUs the snapshot taken shard after shard, are the twin's.
+ * What does not exist: lists of different kinds per copy, host lists, JNI and
+ * C++ mirrors, and a cache of plans between calls. */
+#define IPLS_SEG_COPIES_MAX 1025          /* IPLS_SEG_PEERS_MAX trainers + the received model */
+int ipls_agg_get_partitions_segs_copies(ipls_agg *h,
+                                        void *const *o_ptrs,         /* n_lists * n_segs, list-major */
+                                        int n_lists,
+                                        const int64_t *ns, const int32_t *kinds, int n_segs);
+
 /* ---- observability ----
  * What the last fold launch of a handle (of p's shard for multi-GPU handles:
  * the shard of the last call) ran: the kernel, the tile shape chosen by the
@@ -1015,8 +1053,10 @@ enum {
                                         IPLS_KERNEL_UPDATE_SEGS */
     IPLS_KERNEL_ENCODE_SEGS_DIFF = 17, /* k_b64url_encode_segs_diff (send_gradients_segs_diff): every field as for
                                         IPLS_KERNEL_ENCODE_SEGS */
-    IPLS_KERNEL_UPDATE_SEGS_PEERS = 18 /* k_update_segs_peers (update_gradient_segs_peers): one launch per shard
+    IPLS_KERNEL_UPDATE_SEGS_PEERS = 18,/* k_update_segs_peers (update_gradient_segs_peers): one launch per shard
                                         whatever `owned` repeats; every field as for IPLS_KERNEL_UPDATE_SEGS */
+    IPLS_KERNEL_DIVIDE_SEGS_COPIES = 19 /* k_divide_segs_copies (get_partitions_segs_copies): one launch per shard
+                                        whatever n_lists; every field as for IPLS_KERNEL_DIVIDE_SEGS */
 };
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2

@@ -38,6 +38,7 @@
 #include "seg_kernels.hpp"
 #include "seg_diff_kernels.hpp"
 #include "seg_peers_kernels.hpp"
+#include "seg_copies_kernels.hpp"
 #include "javaser.hpp"
 #include "engine.hpp"
 #include "operand.hpp"
@@ -3436,6 +3437,38 @@ int dev_get_partitions_segs(ipls_dev* h, const seg_ref* segs, int n_segs) {
   });
   HIP_TRY(h, hipGetLastError());
   h->last_launch = launch_info(IPLS_KERNEL_DIVIDE_SEGS, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
+                               (int64_t)l.items.size(), false, false, 0);
+  return IPLS_OK;
+}
+
+// The output-copy-list call: n_lists lists written by one launch.  The plan is the twin's, made from list 0's
+// addresses (segs); the pointer tables of all the lists travel as one [n_lists][n_segs] array in the same upload.
+int dev_get_partitions_segs_copies(ipls_dev* h, const seg_ref* segs, void* const* o_ptrs, int n_lists, int n_segs) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  IPLS_LOCK(h);
+  if (n_lists < 1 || (n_segs > 0 && !o_ptrs)) return fail(h, IPLS_E_INVAL, "bad output copy list");
+  const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
+  const segplan::Plan pl = segplan::plan_divide(seg_geometry(h), tab.data(), n_segs, kSegTile);
+  if (int rc = seg_plan_rc(h, pl)) return rc;
+  const segplan::Launch& l = pl.launches[0];
+  if (l.items.empty()) return IPLS_OK;
+  HIP_TRY(h, dev_use(h->device));
+  std::vector<SegDivPart> parts((size_t)h->P);
+  for (int q = 0; q < h->P; ++q) parts[(size_t)q] = SegDivPart{h->arena + h->w_off[q], h->len[q]};
+  TablePack pack;
+  const size_t at_items = pack.add(l.items.data(), l.items.size());
+  const size_t at_outs = pack.add(o_ptrs, (size_t)n_lists * (size_t)n_segs);
+  const size_t at_parts = pack.add(parts.data(), parts.size());
+  void* d = nullptr;
+  if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &d)) return rc;
+  const char* dt = (const char*)d;
+  with_bool(h->secure != 0, [&](auto sec) {
+    hipLaunchKernelGGL((k_divide_segs_copies<decltype(sec)::value>), dim3((unsigned)l.items.size()), dim3(kBlock), 0,
+                       h->stream, (const segplan::Item*)(dt + at_items), (void* const*)(dt + at_outs), n_lists, n_segs,
+                       (const SegDivPart*)(dt + at_parts), h->chunk, (int64_t)h->p_lo);
+  });
+  HIP_TRY(h, hipGetLastError());
+  h->last_launch = launch_info(IPLS_KERNEL_DIVIDE_SEGS_COPIES, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
                                (int64_t)l.items.size(), false, false, 0);
   return IPLS_OK;
 }

@@ -175,6 +175,11 @@ int64_t dev_send_many_segs_diff(ipls_dev* h, const seg_ref* segs, const void* co
 int dev_update_gradient_segs_peers(ipls_dev* h, const seg_ref* segs, bool diff, const void* const* t_ptrs, int n_peers,
                                    int n_segs, const int32_t* owned, int n_owned);
 
+// The output-copy-list call (ipls_agg_get_partitions_segs_copies; seg_copies_kernels.hpp): n_lists lists over one
+// table, every one written with the twin's bits.  segs is list 0 and makes the plan; o_ptrs[k * n_segs + s] is list
+// k's array of segment s, of segs[s]'s length and format (not looked at when that is empty).  One launch.
+int dev_get_partitions_segs_copies(ipls_dev* h, const seg_ref* segs, void* const* o_ptrs, int n_lists, int n_segs);
+
 // ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
 // One run of a file that an engine packs: `prefix` (framing), then engine
 // partition q's values of `target`, then `suffix` (a byte, or -1).

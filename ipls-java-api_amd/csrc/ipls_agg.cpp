@@ -1475,6 +1475,43 @@ int ipls_agg_get_partitions_segs(ipls_agg* H, void* const* ptrs, const int64_t* 
   return par_shards(H, ss, [&](int s) { return dev_get_partitions_segs(H->sh[s], segs.data(), n_segs); });
 }
 
+// n_lists lists over one table, written as one unit: the twin's checks in the twin's order (the table, the size,
+// then lists 0 .. n_lists-1, then what every shard can reach), all before the first launch on any shard.
+int ipls_agg_get_partitions_segs_copies(ipls_agg* H, void* const* o_ptrs, int n_lists, const int64_t* ns,
+                                        const int32_t* kinds, int n_segs) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (n_lists < 1 || n_lists > IPLS_SEG_COPIES_MAX)
+    return ferr(H, IPLS_E_INVAL, "n_lists %d outside [1, %d]", n_lists, IPLS_SEG_COPIES_MAX);
+  int64_t n = 0;
+  if (int rc = segs_total(H, o_ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (n < H->flat_total)
+    return ferr(H, IPLS_E_RANGE, "output list of %lld < model size %lld", (long long)n, (long long)H->flat_total);
+  std::vector<std::vector<seg_ref>> segs((size_t)n_lists);
+  for (int k = 0; k < n_lists; ++k) {
+    const std::string name = "list " + std::to_string(k);
+    if (int rc = segs_check(H, o_ptrs + (size_t)k * (size_t)n_segs, ns, kinds, n_segs, segs[(size_t)k], name.c_str()))
+      return rc;
+  }
+  const std::vector<int> ss = nonempty_shards(H);
+  if (ss.empty()) return IPLS_OK;
+  if (H->S() > 1)
+    for (int s : ss)
+      for (int k = 0; k < n_lists; ++k)
+        if (int rc = segs_reach(H, s, segs[(size_t)k], H->off[H->lo[s]], H->off[H->lo[s + 1] - 1] + H->chunk,
+                                "output segment"))
+          return rc;
+  std::vector<void*> o((size_t)n_lists * (size_t)n_segs + 1, nullptr);   // an empty segment's pointer is null
+  for (int k = 0; k < n_lists; ++k)
+    for (int s = 0; s < n_segs; ++s)
+      o[(size_t)k * (size_t)n_segs + (size_t)s] = const_cast<void*>(segs[(size_t)k][(size_t)s].ptr);
+  H->last_shard.store(ss.back(), std::memory_order_relaxed);
+  // every shard writes its flat segment [off[lo_s], ...) of the model into every list
+  return par_shards(H, ss, [&](int s) {
+    return dev_get_partitions_segs_copies(H->sh[s], segs[0].data(), o.data(), n_lists, n_segs);
+  });
+}
+
 // ---- UpdateGradient and SendGradients over a segment list, and over the difference of two ----
 // One body each for the plain call (diff false: b_ptrs is not looked at) and the difference call (two pointer
 // tables over one table of lengths and kinds): the same checks in the same order, the subtrahend list after the

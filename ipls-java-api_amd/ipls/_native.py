@@ -41,6 +41,9 @@ KERNEL_UPDATE_SEGS_DIFF, KERNEL_ENCODE_SEGS_DIFF = 16, 17
 # the peer-list call (k_update_segs_peers): K lists over one table, folded in one launch
 KERNEL_UPDATE_SEGS_PEERS = 18
 SEG_PEERS_MAX = 1024
+# the output-copy-list call (k_divide_segs_copies): n_lists lists over one table, written in one launch
+KERNEL_DIVIDE_SEGS_COPIES = 19
+SEG_COPIES_MAX = 1025                        # SEG_PEERS_MAX trainers + the received model
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -176,6 +179,7 @@ SIGNATURES = {
     "ipls_agg_send_gradients_segs": (_i64, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp, _i64, _i,
                                             _vp, _vp]),
     "ipls_agg_get_partitions_segs": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "ipls_agg_get_partitions_segs_copies": (_i, [_vp, _vp, _i, _vp, _vp, _i]),
     # difference lists: a_ptrs (minuend) and b_ptrs (subtrahend) over one ns / kinds table
     "ipls_agg_update_gradient_segs_diff": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i]),
     "ipls_agg_update_gradient_segs_peers": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),

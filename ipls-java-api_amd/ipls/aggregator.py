@@ -223,6 +223,54 @@ class PeerUpdates:
         _, ns, kinds, k = self.peers[0].tables
         return (None if self.received is None else self.received.tables[0]), self._t_ptrs, self.n_peers, ns, kinds, k
 
+    def outputs(self) -> "ModelCopies":
+        """The way back out of the round: the ``ModelCopies`` of ``received``
+        (when there is one) followed by the K trained lists, for
+        ``GetPartitions(out=...)`` to write the new model into all of them in
+        one call."""
+        return ModelCopies(([self.received] if self.received is not None else []) + list(self.peers))
+
+
+class ModelCopies:
+    """Several lists of device tensors of one architecture -- the parameter
+    tensors of K trainers, and the received model they share -- that ONE
+    ``GetPartitions(out=...)`` call writes the averaged model into
+    (include/ipls_agg.h, ``ipls_agg_get_partitions_segs_copies``;
+    k_divide_segs_copies): every list ends with the bits of
+    ``GetPartitions(out=Segments(list))``, W read and divided once, every
+    list from the same W.  ``lists`` holds one list per copy, each a
+    ``Segments``, a list / tuple of CUDA tensors or a single tensor.  Every
+    list must agree with list 0's in number of tensors, ``numel()`` and dtype,
+    else a ValueError naming the list and the tensor, before any library call.
+    The object keeps every tensor alive and can be passed again every round;
+    ``n`` is the number of values, ``n_segs`` the number of tensors per list,
+    ``n_lists`` the number of lists.  Lists that overlap are the caller's
+    problem."""
+
+    def __init__(self, lists):
+        copies = [Difference._list(x) for x in lists]
+        if not 1 <= len(copies) <= N.SEG_COPIES_MAX:
+            raise ValueError(f"need 1 to {N.SEG_COPIES_MAX} lists, not {len(copies)}")
+        first = copies[0]
+        for name, x in [(f"list {k}", c) for k, c in enumerate(copies[1:], 1)]:
+            if x.n_segs != first.n_segs:
+                raise ValueError(f"{name} has {x.n_segs} tensors, list 0 has {first.n_segs}")
+            for i, (a, b) in enumerate(zip(first.tensors, x.tensors)):
+                if a.numel() != b.numel():
+                    raise ValueError(f"{name}, tensor {i}: {b.numel()} elements, list 0 has {a.numel()}")
+                if a.dtype != b.dtype:
+                    raise ValueError(f"{name}, tensor {i}: dtype {b.dtype}, list 0 has {a.dtype}")
+        self.lists = tuple(copies)
+        self.n, self.n_segs, self.n_lists = first.n, first.n_segs, len(copies)
+        k = self.n_segs
+        self._o_ptrs = (ctypes.c_void_p * max(k * self.n_lists, 1))(*[c.tables[0][s] for c in copies for s in range(k)])
+
+    @property
+    def tables(self):
+        """(o_ptrs, n_lists, ns, kinds, n_segs) as the C call takes them."""
+        _, ns, kinds, k = self.lists[0].tables
+        return self._o_ptrs, self.n_lists, ns, kinds, k
+
 
 def _segments(x):
     """x as a Segments when it is one, or a list / tuple of CUDA tensors (wrapped on the fly); else None."""
@@ -344,6 +392,8 @@ def _operand(x, big_endian: bool = False, f32: bool = False):
         raise TypeError("a Difference is an operand of UpdateGradient and SendGradients only")
     if isinstance(x, PeerUpdates):
         raise TypeError("a PeerUpdates is an operand of UpdateGradient only")
+    if isinstance(x, ModelCopies):
+        raise TypeError("a ModelCopies is an output of GetPartitions only")
     if isinstance(x, DeviceBuffer):
         return x.ptr, x.n, x.kind, x
     return _host_operand(x, big_endian, f32)
@@ -1041,12 +1091,17 @@ class Aggregator:
         patterns) gets that float rounded again to the 16-bit format, 2 bytes
         per value.  A ``Segments`` ``out`` (the model's parameter tensors)
         gets every tensor written in its own dtype by those same rules, with
-        no flat model and no copy-out in between."""
+        no flat model and no copy-out in between; a ``ModelCopies`` ``out``
+        (K trainers' tensors and the received model) gets every one of its
+        lists written so, by one call."""
         n = self.flat_size
         if isinstance(out, Difference):
             raise TypeError("a Difference is an operand of UpdateGradient and SendGradients only, not an output")
         if isinstance(out, PeerUpdates):
             raise TypeError("a PeerUpdates is an operand of UpdateGradient only, not an output")
+        if isinstance(out, ModelCopies):   # every list of one architecture in one launch (k_divide_segs_copies)
+            self._chk(self._lib.ipls_agg_get_partitions_segs_copies(self._h, *out.tables))
+            return out
         if isinstance(out, Segments):   # straight into the model's tensors, each in its own dtype (k_divide_segs)
             self._chk(self._lib.ipls_agg_get_partitions_segs(self._h, *out.tables))
             return out
