@@ -1002,6 +1002,67 @@ int ipls_agg_get_partitions_segs_copies(ipls_agg *h,
                                         int n_lists,
                                         const int64_t *ns, const int32_t *kinds, int n_segs);
 
+/* ---- the many-trainers round over tensor lists in one call ----
+ *
+ * What closes an iteration of the many-trainers experiment on one GPU: the K
+ * trainers' lists folded, AggregatePartition of the owned partitions, and the
+ * new model written back into every trainer's arrays.  The end state -- W,
+ * the accumulators' logically-zero states, the count slots and every output
+ * list -- is, bit for bit, that of these three steps made under ONE hold of
+ * each shard's lock:
+ *   1. ipls_agg_update_gradient_segs_peers(h, m_ptrs, t_ptrs, n_peers, ns,
+ *      kinds, n_segs, owned, n_owned);
+ *   2. ipls_agg_finalize(h, p, NULL, 0, NULL) for every distinct p in `owned`;
+ *   3. ipls_agg_get_partitions_segs_copies(h, o_ptrs, n_lists, ns, kinds,
+ *      n_segs).
+ * A partition in `owned`: queued arrivals of its shard are folded first; the
+ * fold is (((start + v_0) .. mult times) + v_1 ..) + v_{K-1}, start = +0.0
+ * where AGG is logically zero, the count-slot and tail rules the peer-list
+ * call's; W = that + REP by exactly k_finalize's operation (REP logically
+ * zero: an addition of +0.0, so a -0.0 sum becomes +0.0); AGG and REP are left
+ * in place and flagged logically zero -- AGG is never stored.  A partition
+ * not in `owned`: W is read only.  Every partition: each list k gets
+ * narrow_kind(W[i] / W[L_p - 1]) by the output-copy-list call's rules (always
+ * the IEEE double division, one rounding to F32, the two-step rule for F16 /
+ * BF16, zero-count passthrough, secure mode's 1e12 * cnt, nothing at or past
+ * the model size).  The count a partition is divided by is its final count
+ * slot: for an owned one ((AGG_slot or +0.0) + 1.0 added K * mult times one
+ * after another) + REP_slot.
+ * ALIASING is part of the contract: an output list may be the very arrays of
+ * the minuend list or of any peer list -- the same pointer for the same
+ * segment of the same table -- which is the main use (the trainers' own
+ * parameters and the received model take the new model in place).  Every
+ * read the call makes of an element happens before any write of it, and the
+ * result is the one computed from the values before the call.  Any other
+ * overlap between an output and an input or another output is the caller's
+ * problem.
+ * Every check runs before the first launch on any shard, and a refusal leaves
+ * every accumulator, flag, queued arrival, W and list byte as it was:
+ * n_peers outside [1, IPLS_SEG_PEERS_MAX], n_lists outside
+ * [1, IPLS_SEG_COPIES_MAX], a NULL t_ptrs, a NULL o_ptrs with n_segs > 0
+ * (IPLS_E_INVAL); then the peer-list call's checks in its order (geometry,
+ * `owned`, the minuend, peers 0 .. K-1); then the output-copy-list call's
+ * (n < the flat size is IPLS_E_RANGE, then lists 0 .. n_lists-1, the messages
+ * naming the segment and "list k"); then, on a handle over several GPUs, that
+ * every array of every list a shard touches is memory its device can reach
+ * (IPLS_E_DEVICE).  Both bounds together leave n == the flat size.
+ * n_owned == 0 is the divide into the lists alone.  n_peers == 1 and
+ * n_lists == 1 run this call's own kernel too (ipls_agg_last_launch says
+ * IPLS_KERNEL_ROUND_SEGS_PEERS).  On a handle over several GPUs the shards
+ * are taken one after another, each shard's part under one hold of its lock
+ * and in one launch; the model-wide snapshot caveat is the output-copy-list
+ * call's.
+ * What does not exist: per-list dtypes, host lists, a fused send, JNI and C++
+ * mirrors, and a cache of plans between calls. */
+int ipls_agg_round_segs_peers(ipls_agg *h,
+                              const void *const *m_ptrs,   /* n_segs minuend pointers (the received model), or NULL */
+                              const void *const *t_ptrs,   /* n_peers * n_segs, peer-major */
+                              int n_peers,
+                              void *const *o_ptrs,         /* n_lists * n_segs, list-major */
+                              int n_lists,
+                              const int64_t *ns, const int32_t *kinds, int n_segs,
+                              const int32_t *owned, int n_owned);
+
 /* ---- observability ----
  * What the last fold launch of a handle (of p's shard for multi-GPU handles:
  * the shard of the last call) ran: the kernel, the tile shape chosen by the
@@ -1055,8 +1116,12 @@ enum {
                                         IPLS_KERNEL_ENCODE_SEGS */
     IPLS_KERNEL_UPDATE_SEGS_PEERS = 18,/* k_update_segs_peers (update_gradient_segs_peers): one launch per shard
                                         whatever `owned` repeats; every field as for IPLS_KERNEL_UPDATE_SEGS */
-    IPLS_KERNEL_DIVIDE_SEGS_COPIES = 19 /* k_divide_segs_copies (get_partitions_segs_copies): one launch per shard
+    IPLS_KERNEL_DIVIDE_SEGS_COPIES = 19,/* k_divide_segs_copies (get_partitions_segs_copies): one launch per shard
                                         whatever n_lists; every field as for IPLS_KERNEL_DIVIDE_SEGS */
+    IPLS_KERNEL_ROUND_SEGS_PEERS = 20  /* k_round_segs_peers (round_segs_peers): one launch per shard, one block per
+                                        tile of EVERY partition of the shard, owned or not; seqf as for
+                                        IPLS_KERNEL_UPDATE_SEGS; start ZERO when every owned partition's AGG was
+                                        logically zero, else ACCUM; 0 when nothing is owned (the divide alone) */
 };
 #define IPLS_SHAPE_BIG    1
 #define IPLS_SHAPE_MID    2

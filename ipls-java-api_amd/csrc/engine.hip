@@ -39,6 +39,7 @@
 #include "seg_diff_kernels.hpp"
 #include "seg_peers_kernels.hpp"
 #include "seg_copies_kernels.hpp"
+#include "seg_round_kernels.hpp"
 #include "javaser.hpp"
 #include "engine.hpp"
 #include "operand.hpp"
@@ -3470,6 +3471,93 @@ int dev_get_partitions_segs_copies(ipls_dev* h, const seg_ref* segs, void* const
   HIP_TRY(h, hipGetLastError());
   h->last_launch = launch_info(IPLS_KERNEL_DIVIDE_SEGS_COPIES, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
                                (int64_t)l.items.size(), false, false, 0);
+  return IPLS_OK;
+}
+
+// The many-trainers round: the fold of the peer-list call, W = AGG + REP and the divide of the output-copy-list call
+// in one launch over ALL the shard's partitions (the plan is the update's, over 0 .. P-1 in ascending order, so no
+// destination tile belongs to two items).  A partition's multiplicity in `owned` goes into its job; 0 means not
+// owned: W is read and divided only.  The logically-zero flags go to the kernel as they are -- nothing is
+// materialized, AGG is never stored -- and every owned partition leaves with both set.
+int dev_round_segs_peers(ipls_dev* h, const seg_ref* segs, bool diff, const void* const* t_ptrs, int n_peers,
+                         void* const* o_ptrs, int n_lists, int n_segs, const int32_t* owned, int n_owned) {
+  if (!h) return fail(nullptr, IPLS_E_INVAL, "null handle");
+  IPLS_LOCK(h);
+  if (n_peers < 1 || !t_ptrs) return fail(h, IPLS_E_INVAL, "bad peer list");
+  if (n_lists < 1 || (n_segs > 0 && !o_ptrs)) return fail(h, IPLS_E_INVAL, "bad output copy list");
+  if (n_owned < 0 || (n_owned > 0 && !owned)) return fail(h, IPLS_E_INVAL, "bad owned list");
+  std::vector<int32_t> mult((size_t)h->P, 0), all((size_t)h->P);
+  for (int i = 0; i < n_owned; ++i) {
+    if (int rc = check_part(h, owned[i])) return rc;
+    ++mult[(size_t)owned[i]];
+  }
+  for (int q = 0; q < h->P; ++q) all[(size_t)q] = q;
+  const std::vector<segplan::Seg> tab = seg_table(segs, n_segs);
+  const segplan::Plan pl = segplan::plan_update(seg_geometry(h), tab.data(), n_segs, all.data(), h->P, kSegTile);
+  if (int rc = seg_plan_rc(h, pl)) return rc;
+  if (pl.n < h->flat_total)
+    return fail(h, IPLS_E_RANGE, "output list of %lld < model size %lld", (long long)pl.n, (long long)h->flat_total);
+  if (h->P == 0) return IPLS_OK;
+  const segplan::Launch& l = pl.launches[0];          // no repeats: one launch
+  // both twins' bounds together: every partition's values are its whole body, and the pieces are the shard's model
+  int64_t covered = 0;
+  for (const segplan::Job& j : l.jobs) {
+    if (j.ncopy != j.L - 1)
+      return fail(h, IPLS_E_RANGE, "partition %d holds %lld values, the lists give it %lld", h->p_lo + j.q,
+                  (long long)(j.L - 1), (long long)j.ncopy);
+    covered += j.ncopy;
+  }
+  int64_t in_pieces = 0;
+  for (const segplan::Piece& p : pl.pieces) in_pieces += p.n;
+  if (covered != in_pieces || covered != h->flat_total - h->flat_base)
+    return fail(h, IPLS_E_RANGE, "the lists' %lld values on this shard are not its %lld model values",
+                (long long)in_pieces, (long long)(h->flat_total - h->flat_base));
+  if (l.items.empty()) return IPLS_OK;
+  HIP_TRY(h, dev_use(h->device));
+  const std::vector<SegPiece> pieces = seg_pieces(pl, segs);
+  std::vector<const void*> psrc(pieces.size() * (size_t)n_peers);
+  std::vector<void*> pdst(pieces.size() * (size_t)n_lists);
+  for (size_t k = 0; k < pieces.size(); ++k) {
+    const segplan::Piece& p = pl.pieces[k];
+    const int64_t at = p.src * segplan::fmt_esz(segs[p.seg].fmt);
+    for (int q = 0; q < n_peers; ++q)
+      psrc[k * (size_t)n_peers + (size_t)q] = (const char*)t_ptrs[(size_t)q * (size_t)n_segs + (size_t)p.seg] + at;
+    for (int q = 0; q < n_lists; ++q)
+      pdst[k * (size_t)n_lists + (size_t)q] = (char*)o_ptrs[(size_t)q * (size_t)n_segs + (size_t)p.seg] + at;
+  }
+  std::vector<SegRoundJob> jobs(l.jobs.size());
+  bool all_zero = n_owned > 0;   // the divide alone starts nothing: 0, as the divide twins report
+  for (size_t j = 0; j < jobs.size(); ++j) {
+    const int q = l.jobs[j].q;
+    jobs[j] = SegRoundJob{(const unsigned long long*)(h->arena + h->agg_off[q]),
+                          (const unsigned long long*)(h->arena + h->rep_off[q]),
+                          (unsigned long long*)(h->arena + h->w_off[q]), l.jobs[j].ncopy, l.jobs[j].L,
+                          h->agg_zero[q] ? 1 : 0, h->rep_zero[q] ? 1 : 0, mult[(size_t)q], 0};
+    if (mult[(size_t)q]) all_zero = all_zero && h->agg_zero[q];
+  }
+  TablePack pack;
+  const size_t at_items = pack.add(l.items.data(), l.items.size());
+  const size_t at_jobs = pack.add(jobs.data(), jobs.size());
+  const size_t at_pieces = pack.add(pieces.data(), pieces.size());
+  const size_t at_psrc = pack.add(psrc.data(), psrc.size());
+  const size_t at_pdst = pack.add(pdst.data(), pdst.size());
+  void* d = nullptr;
+  if (int rc = upload_table(h, pack.bytes.data(), pack.bytes.size(), &d)) return rc;
+  const char* dt = (const char*)d;
+  with_bool(diff, [&](auto df) {
+    with_bool(h->secure != 0, [&](auto sec) {
+      hipLaunchKernelGGL((k_round_segs_peers<decltype(df)::value, decltype(sec)::value>),
+                         dim3((unsigned)l.items.size()), dim3(kBlock), 0, h->stream,
+                         (const segplan::Item*)(dt + at_items), (const SegRoundJob*)(dt + at_jobs),
+                         (const SegPiece*)(dt + at_pieces), (const void* const*)(dt + at_psrc), n_peers,
+                         (void* const*)(dt + at_pdst), n_lists);
+    });
+  });
+  HIP_TRY(h, hipGetLastError());
+  for (int q = 0; q < h->P; ++q)
+    if (mult[(size_t)q]) h->agg_zero[q] = h->rep_zero[q] = 1;
+  h->last_launch = launch_info(IPLS_KERNEL_ROUND_SEGS_PEERS, 0, kBlock, kSegV, l.any_whole ? 1 : 0, 0,
+                               (int64_t)l.items.size(), false, false, all_zero ? kZero : kAccum);
   return IPLS_OK;
 }
 

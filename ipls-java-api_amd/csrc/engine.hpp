@@ -180,6 +180,14 @@ int dev_update_gradient_segs_peers(ipls_dev* h, const seg_ref* segs, bool diff, 
 // k's array of segment s, of segs[s]'s length and format (not looked at when that is empty).  One launch.
 int dev_get_partitions_segs_copies(ipls_dev* h, const seg_ref* segs, void* const* o_ptrs, int n_lists, int n_segs);
 
+// The many-trainers round (ipls_agg_round_segs_peers; seg_round_kernels.hpp): the peer-list fold, W = AGG + REP and
+// the output-copy-list divide of the engine's partitions in one launch.  segs, diff, t_ptrs and n_peers as for
+// dev_update_gradient_segs_peers, o_ptrs and n_lists as for dev_get_partitions_segs_copies; `owned` lists the
+// engine partitions that are folded and finalized (repeats are multiplicities), every other partition's W is read
+// only.  An output list may be the minuend list or a peer list (same arrays).
+int dev_round_segs_peers(ipls_dev* h, const seg_ref* segs, bool diff, const void* const* t_ptrs, int n_peers,
+                         void* const* o_ptrs, int n_lists, int n_segs, const int32_t* owned, int n_owned);
+
 // ---- saved-model files (javaser.hpp; ipls_agg_save_model* / _load_saved) ----
 // One run of a file that an engine packs: `prefix` (framing), then engine
 // partition q's values of `target`, then `suffix` (a byte, or -1).

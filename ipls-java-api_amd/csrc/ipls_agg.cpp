@@ -1683,6 +1683,74 @@ int ipls_agg_update_gradient_segs_peers(ipls_agg* H, const void* const* m_ptrs, 
                                           (int)per[s].size());
   });
 }
+// The many-trainers round: fold, W = AGG + REP and the divide into n_lists lists as one unit per shard.  The update
+// twin's checks in its order, then the divide twin's, then what every shard can reach, all before the first launch
+// on any shard; then shard after shard, each under one hold of its lock, one launch each.
+int ipls_agg_round_segs_peers(ipls_agg* H, const void* const* m_ptrs, const void* const* t_ptrs, int n_peers,
+                              void* const* o_ptrs, int n_lists, const int64_t* ns, const int32_t* kinds, int n_segs,
+                              const int32_t* owned, int n_owned) {
+  KeepDevice keep_device;
+  if (!H) return ferr(nullptr, IPLS_E_INVAL, "null handle");
+  if (n_peers < 1 || n_peers > IPLS_SEG_PEERS_MAX)
+    return ferr(H, IPLS_E_INVAL, "n_peers %d outside [1, %d]", n_peers, IPLS_SEG_PEERS_MAX);
+  if (n_lists < 1 || n_lists > IPLS_SEG_COPIES_MAX)
+    return ferr(H, IPLS_E_INVAL, "n_lists %d outside [1, %d]", n_lists, IPLS_SEG_COPIES_MAX);
+  if (!t_ptrs) return ferr(H, IPLS_E_INVAL, "bad segment table: null peer list");
+  if (n_segs > 0 && !o_ptrs) return ferr(H, IPLS_E_INVAL, "bad segment table: null output list");
+  int64_t n = 0;
+  if (int rc = segs_total(H, t_ptrs, ns, kinds, n_segs, &n)) return rc;
+  if (int rc = segs_bounds(H, n)) return rc;
+  if (n_owned < 0 || (n_owned > 0 && !owned)) return ferr(H, IPLS_E_INVAL, "bad owned list");
+  for (int i = 0; i < n_owned; ++i)
+    if (!part_ok(H, owned[i])) return range_err(H, owned[i]);
+  const bool diff = m_ptrs != nullptr;
+  std::vector<seg_ref> m_segs;
+  std::vector<std::vector<seg_ref>> t_segs((size_t)n_peers), o_segs((size_t)n_lists);
+  if (diff)
+    if (int rc = segs_check(H, m_ptrs, ns, kinds, n_segs, m_segs, "minuend")) return rc;
+  for (int k = 0; k < n_peers; ++k) {
+    const std::string name = "peer " + std::to_string(k);
+    if (int rc = segs_check(H, t_ptrs + (size_t)k * (size_t)n_segs, ns, kinds, n_segs, t_segs[(size_t)k], name.c_str()))
+      return rc;
+  }
+  if (n < H->flat_total)
+    return ferr(H, IPLS_E_RANGE, "output list of %lld < model size %lld", (long long)n, (long long)H->flat_total);
+  for (int k = 0; k < n_lists; ++k) {
+    const std::string name = "list " + std::to_string(k);
+    if (int rc = segs_check(H, o_ptrs + (size_t)k * (size_t)n_segs, ns, kinds, n_segs, o_segs[(size_t)k], name.c_str()))
+      return rc;
+  }
+  const std::vector<int> ss = nonempty_shards(H);
+  if (ss.empty()) return IPLS_OK;
+  if (H->S() > 1)
+    for (int s : ss) {
+      const int64_t lo = H->off[H->lo[s]], hi = H->off[H->lo[s + 1] - 1] + H->chunk;
+      if (int rc = segs_reach(H, s, m_segs, lo, hi, "minuend segment")) return rc;
+      for (int k = 0; k < n_peers; ++k)
+        if (int rc = segs_reach(H, s, t_segs[(size_t)k], lo, hi, "peer segment")) return rc;
+      for (int k = 0; k < n_lists; ++k)
+        if (int rc = segs_reach(H, s, o_segs[(size_t)k], lo, hi, "output segment")) return rc;
+    }
+  // an empty segment's pointer is null
+  std::vector<const void*> t((size_t)n_peers * (size_t)n_segs + 1, nullptr);
+  std::vector<void*> o((size_t)n_lists * (size_t)n_segs + 1, nullptr);
+  for (int s = 0; s < n_segs; ++s) {
+    for (int k = 0; k < n_peers; ++k) t[(size_t)k * (size_t)n_segs + (size_t)s] = t_segs[(size_t)k][(size_t)s].ptr;
+    for (int k = 0; k < n_lists; ++k)
+      o[(size_t)k * (size_t)n_segs + (size_t)s] = const_cast<void*>(o_segs[(size_t)k][(size_t)s].ptr);
+  }
+  const std::vector<seg_ref>& plan = diff ? m_segs : t_segs[0];
+  std::vector<std::vector<int32_t>> per(H->S());
+  for (int i = 0; i < n_owned; ++i) per[H->owner[owned[i]]].push_back(owned[i] - H->lo[H->owner[owned[i]]]);
+  for (int s : ss) {   // shard after shard: every shard reads and writes its own flat segment of every list
+    H->last_shard.store(s, std::memory_order_relaxed);
+    if (int rc = dev_round_segs_peers(H->sh[s], plan.data(), diff, t.data(), n_peers, o.data(), n_lists, n_segs,
+                                      per[s].data(), (int)per[s].size());
+        rc < 0)
+      return fwd(H, s, rc);
+  }
+  return IPLS_OK;
+}
 int64_t ipls_agg_send_gradients_segs(ipls_agg* H, const void* const* ptrs, const int64_t* ns, const int32_t* kinds,
                                      int n_segs, const int32_t* parts, int n_parts, int32_t iteration, int16_t pid,
                                      const uint8_t* origin, int32_t origin_len, void* out, int64_t out_cap,

@@ -11,6 +11,7 @@ from ._native import (  # noqa: F401
     KERNEL_ROUND_F32, KERNEL_ROUND_H16, KERNEL_FOLD1_F32, KERNEL_FOLD1_H16, KERNEL_UPDATE_FLAT, KERNEL_ENCODE_FLAT,
     KERNEL_UPDATE_SEGS, KERNEL_DIVIDE_SEGS, KERNEL_ENCODE_SEGS, KERNEL_UPDATE_SEGS_DIFF, KERNEL_ENCODE_SEGS_DIFF,
     KERNEL_UPDATE_SEGS_PEERS, SEG_PEERS_MAX, KERNEL_DIVIDE_SEGS_COPIES, SEG_COPIES_MAX,
+    KERNEL_ROUND_SEGS_PEERS,
     HOST_TEXT, KERNEL_FOLD1, KERNEL_REDUCE, KERNEL_REDUCE_SCALAR, KERNEL_ROUND, SHAPE_BIG, SHAPE_HALF, SHAPE_MID,
     SHAPE_SMALL, START_ACCUM, START_FIRST, START_ZERO, TGT_AGG, TGT_FUTURE, TGT_REP, TGT_WADDR, TGT_WEIGHTS,
     SAVED_BLEND, SAVED_SET, IplsError, build_info, lib,

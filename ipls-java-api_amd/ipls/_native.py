@@ -44,6 +44,8 @@ SEG_PEERS_MAX = 1024
 # the output-copy-list call (k_divide_segs_copies): n_lists lists over one table, written in one launch
 KERNEL_DIVIDE_SEGS_COPIES = 19
 SEG_COPIES_MAX = 1025                        # SEG_PEERS_MAX trainers + the received model
+# the many-trainers round (k_round_segs_peers): the peer-list fold, W = AGG + REP and the copy-list divide, one launch
+KERNEL_ROUND_SEGS_PEERS = 20
 SHAPE_BIG, SHAPE_MID, SHAPE_SMALL, SHAPE_HALF = 1, 2, 3, 4
 ABI_VERSION = 4
 START_ACCUM, START_ZERO, START_FIRST = 0, 1, 2
@@ -183,6 +185,8 @@ SIGNATURES = {
     # difference lists: a_ptrs (minuend) and b_ptrs (subtrahend) over one ns / kinds table
     "ipls_agg_update_gradient_segs_diff": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i]),
     "ipls_agg_update_gradient_segs_peers": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i]),
+    # the round over a peer list and an output copy list: m_ptrs, t_ptrs, n_peers, o_ptrs, n_lists, the table, owned
+    "ipls_agg_round_segs_peers": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i]),
     "ipls_agg_send_gradients_segs_diff": (_i64, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i32, _i16, _vp, _i32, _vp,
                                                  _i64, _i, _vp, _vp]),
     "ipls_agg_last_launch": (_i, [_vp, _P(LaunchInfo)]),

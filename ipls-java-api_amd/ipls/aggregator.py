@@ -567,6 +567,36 @@ class Aggregator:
         self._chk(self._lib.ipls_agg_update_gradient(
             self._h, ptr, n, kind, owned.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(owned)))
 
+    def round_peers(self, peers, auth_list, out=None):
+        """The many-trainers round in one call (include/ipls_agg.h,
+        ``ipls_agg_round_segs_peers``; k_round_segs_peers): the state and the
+        bits of ``UpdateGradient(peers, auth_list)``, ``AggregatePartition`` of
+        every partition in ``auth_list`` and ``GetPartitions(out=out)``, made
+        under one hold of each shard's lock in one launch per shard.
+        ``peers`` is a ``PeerUpdates``; ``out`` a ``ModelCopies`` over the
+        same table, or ``None`` for ``peers.outputs()``: the trainers'
+        tensors (and the received model) take the new model in place.
+        Returns ``out``."""
+        if not isinstance(peers, PeerUpdates):
+            raise TypeError(f"round_peers folds a PeerUpdates, not a {type(peers).__name__}")
+        if out is None:
+            out = peers.outputs()
+        elif not isinstance(out, ModelCopies):
+            raise TypeError(f"round_peers writes into a ModelCopies (or None: peers.outputs()), not a {type(out).__name__}")
+        first = peers.peers[0]
+        if out.n_segs != first.n_segs:
+            raise ValueError(f"out has {out.n_segs} tensors per list, the peers have {first.n_segs}")
+        for i, (a, b) in enumerate(zip(first.tensors, out.lists[0].tensors)):
+            if a.numel() != b.numel():
+                raise ValueError(f"out, tensor {i}: {b.numel()} elements, the peers have {a.numel()}")
+            if a.dtype != b.dtype:
+                raise ValueError(f"out, tensor {i}: dtype {b.dtype}, the peers have {a.dtype}")
+        owned = np.ascontiguousarray(np.asarray(list(auth_list), dtype=np.int32))
+        m_ptrs, t_ptrs, n_peers, ns, kinds, k = peers.tables
+        self._chk(self._lib.ipls_agg_round_segs_peers(self._h, m_ptrs, t_ptrs, n_peers, out.tables[0], out.n_lists, ns,
+                                                      kinds, k, owned.ctypes.data, len(owned)))
+        return out
+
     def Update(self, gradient, partition: int, from_clients: bool = True, *, frame: bool = False,
                pair: bool = False, from_future: bool = False):
         """Updater._Update: client buckets fold into Aggregated_Gradients
